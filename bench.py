@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W          (any N: for N > 1 without a launcher's environment this process
                                                             starts the N ranks itself, as fresh child processes)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1 under a launcher)
+    python bench.py ... --dump-outputs DIR                  (also writes what the last timed step computed: dump_outputs)
 
 Metric (BASELINE.json): batched FWHT Gtransforms/s (one transform = one length-D row) with the
 achieved HBM GB/s against the roofline.  Workload = the configuration the metric's target is
@@ -52,7 +53,12 @@ def parse():
     ap.add_argument("--log2d", type=int, default=LOG2D)
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(n_gpus):
@@ -170,6 +176,25 @@ def timed(step, steps, warmup, device, world):
                     "ms_per_step_kernel_events": [round(float(b[1]), 4) for b in both]}
         wall = max(float(b[0]) for b in both) * steps / 1e3
     return wall, ev_ms, per_rank
+
+
+DUMP_BYTES = 32 << 20     # per run, split over the ranks: the bound is 64 MB
+
+
+def dump_outputs(out_dir, x, rank, world):
+    """Write the buffer as the last timed step left it -- what a caller of the in-place transform receives -- as float32
+    ``fwht_rows.npy``: a fixed sample of rows (seeded, ascending; every row when they fit in DUMP_BYTES), with their
+    indices as float64 in ``fwht_row_index.npy``.  Ranks of an N > 1 run write ``..._rank<r>.npy``."""
+    import numpy as np
+    rows, d = x.shape
+    keep = max(1, DUMP_BYTES // world // (d * x.element_size()))
+    idx = torch.arange(rows)
+    if keep < rows:
+        idx = torch.randperm(rows, generator=torch.Generator().manual_seed(2024))[:keep].sort().values
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, f"fwht_rows{suffix}.npy"), x[idx.to(x.device)].float().cpu().numpy())
+    np.save(os.path.join(out_dir, f"fwht_row_index{suffix}.npy"), idx.numpy().astype(np.float64))
 
 
 def event_ms(fn, iters=10, warm=2, warm_ms=0.0):
@@ -927,6 +952,8 @@ def main():
     step = make_step(x)
 
     wall, ev_ms, per_rank = timed(step, args.steps, args.warmup, device, world)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, x, rank, world)
     finite = bool(torch.isfinite(x[:: max(1, rows // 64)]).all())
     if device.type == "cuda":
         kernel_symbol = _hip.last_kernel()       # what the library's dispatch actually launched for this shape

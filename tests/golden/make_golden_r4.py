@@ -9,7 +9,12 @@ config4_real_size_golden.npz -- BASELINE config 4's network, ``WHVIRegression`` 
 over src/layers.py:31-38: a stacked layer of 256 D = 4 sub-matrices, a square D = 1024 layer, a transposed column layer), at a
 REAL batch: 512 rows x 16 Monte-Carlo samples (one GPU's share of the 128) in eval mode -- the predictions
 ``net(x)`` of shape (512, 1, 16) with every eps the reference drew recorded in draw order, plus ``eval_model``'s RMSE / MNLL
-of them (src/networks.py:101-115,130-133).  The round-2 fixture of the same network holds batch 6 x 3 samples."""
+of them (src/networks.py:101-115,130-133).  The round-2 fixture of the same network holds batch 6 x 3 samples.
+
+The host dispatch's dense H matmul rounds differently on MKL's AVX-512 and AVX2 kernels (the latter is what AMD hosts get).
+A second run with the AVX2 kernels forced adds that run's host record as pred_avx2 / rmse_avx2 / mnll_avx2 and keeps the rest:
+
+    MKL_ENABLE_INSTRUCTIONS=AVX2 python tests/golden/make_golden_r4.py --avx2"""
 import os
 import sys
 
@@ -108,7 +113,13 @@ def main():
     out["rmse_butterfly"], out["mnll_butterfly"] = np.array(rmse_b, dtype=np.float64), np.array(mnll_b, dtype=np.float64)
     print("butterfly dispatch vs dense-H dispatch of the reference itself: max |diff| / max |pred| =",
           float(np.abs(out["pred_butterfly"] - out["pred"]).max() / np.abs(out["pred"]).max()))
-    np.savez_compressed(os.path.join(HERE, "config4_real_size_golden.npz"), **out)
+    path = os.path.join(HERE, "config4_real_size_golden.npz")
+    if "--avx2" in sys.argv[1:]:
+        assert os.environ.get("MKL_ENABLE_INSTRUCTIONS") == "AVX2", "run with MKL_ENABLE_INSTRUCTIONS=AVX2"
+        kept = dict(np.load(path))
+        assert all(np.array_equal(kept[k], out[k]) for k in ("x", "y", "params", "eps_layer0", "eps_layer1", "eps_layer2"))
+        out = {**kept, "pred_avx2": out["pred"], "rmse_avx2": out["rmse"], "mnll_avx2": out["mnll"]}
+    np.savez_compressed(path, **out)
     print("config4_real_size_golden.npz: pred", out["pred"].shape, "max |pred|", float(np.abs(out["pred"]).max()),
           "std over samples", float(out["pred"].std(axis=2).mean()), "rmse", rmse, "mnll", mnll,
           "bytes", os.path.getsize(os.path.join(HERE, "config4_real_size_golden.npz")))

@@ -567,7 +567,9 @@ def run_config4_real_size(device, monkeypatch):
     route (dense H matmul for D < 4096) and ``pred_butterfly`` = the GPU route (butterfly FWHT for every matrix; the
     reference's own vectorised FWHT standing in for its CUDA kernel).  They differ by 2.8e-5 of the largest prediction (the
     dense H product leaves ~1e-7 off-diagonals in the exactly diagonal as-written weight); each device is compared with the
-    record of ITS dispatch at 1e-5 and with the other one at 1e-4."""
+    record of ITS dispatch at 1e-5 and with the other one at 1e-4.  The host record exists twice, as the reference computed it
+with MKL's AVX-512 and with its AVX2 kernels (``pred`` / ``pred_avx2``: the dense H products round differently, 2.9e-5
+apart); the host route is held to the closer of the two."""
     g = _npz("config4_real_size_golden.npz")
     mine, other = ("pred", "pred_butterfly") if device == "cpu" else ("pred_butterfly", "pred")
     tag = "" if device == "cpu" else "_butterfly"
@@ -583,6 +585,9 @@ def run_config4_real_size(device, monkeypatch):
         pred = net.forward_batched(x, S)
     monkeypatch.undo()
     assert pred.shape == (512, 1, 16)
+    if device == "cpu":
+        tag = min(("", "_avx2"), key=lambda t: _rel(pred.numpy(), g["pred" + t]))
+        mine = "pred" + tag
     assert _rel(pred.cpu().numpy(), g[mine]) <= 1e-5
     assert _rel(pred.cpu().numpy(), g[other]) <= 1e-4
     # ... which is far below what distinguishes one Monte-Carlo sample from another

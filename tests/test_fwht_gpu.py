@@ -436,16 +436,18 @@ def test_last_kernel_names_the_launched_instantiation(hip_lib):
     assert _hip.last_kernel().startswith("whvi::fused_shs_kernel<float, 12, 16, 1, false, ")
 
 
-def test_bench_line_on_the_gpu(hip_lib):
+def test_bench_line_on_the_gpu(hip_lib, tmp_path):
     """bench.py end to end at a small row count: one JSON line with the contract fields, the roofline object naming
-    the kernel that was launched, and a traffic value or an explicit reason why there is none for this shape."""
+    the kernel that was launched, and a traffic value or an explicit reason why there is none for this shape; the rows
+    ``--dump-outputs`` samples (1 GiB buffer: 2048 rows) are four transforms of bench.py's seeded input, bit for bit."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--rows", "65536", "--steps", "3", "--warmup", "1",
-                          "--no-extras", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
+                          "--no-extras", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=root)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -460,6 +462,15 @@ def test_bench_line_on_the_gpu(hip_lib):
     assert roof["kernel"].startswith("whvi::fwht_rows_kernel<float, 12, 16, ")
     assert roof["traffic"] is None and "no PMC record" in roof["traffic_note"]          # only the headline shape has one
     assert rec["config"]["values_finite_after_run"] is True
+    rows, idx = np.load(tmp_path / "fwht_rows.npy"), np.load(tmp_path / "fwht_row_index.npy")
+    assert rows.shape == (2048, 4096) and rows.dtype == np.float32 and idx.dtype == np.float64
+    assert np.all(np.diff(idx) > 0) and idx[-1] < 65536
+    x = torch.randn(65536, 4096, device=DEV, generator=torch.Generator(device=DEV).manual_seed(1234))
+    want = x[torch.from_numpy(idx.astype(np.int64)).to(DEV)].cpu().numpy() * np.float32(2.0 ** -24)   # bench.py's input
+    del x
+    for _ in range(4):
+        want = oracle.fwht(want)
+    assert np.array_equal(rows.view(np.uint32), want.view(np.uint32))
 
 
 @pytest.mark.parametrize("dtype,log2d", [(torch.float32, 9), (torch.float32, 10), (torch.float32, 11),

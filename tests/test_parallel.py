@@ -279,6 +279,39 @@ def test_bench_two_ranks_gloo_cpu_plumbing(tmp_path):
     assert rec["distributed"]["backend"] == "gloo" and rec["distributed"]["world_size"] == 2
 
 
+def test_bench_dump_outputs_cpu_plumbing(tmp_path):
+    """``--dump-outputs DIR`` writes what the last timed step left in the buffer: with --steps 3 --warmup 2 that is
+    exactly five transforms of bench.py's seeded input (here every row, as float32, bit-equal to the oracle), and a
+    second run with the same arguments writes the same bytes."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    import oracle
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["WHVI_BENCH_CPU_PLUMBING"] = "1"
+    dumps = []
+    for run in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--log2d", "6",
+                              "--dump-outputs", str(tmp_path / run)], env=env, cwd=root, capture_output=True, text=True,
+                             timeout=300)
+        assert out.returncode == 0, out.stderr[-2000:]
+        rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / run)) == ["fwht_row_index.npy", "fwht_rows.npy"]
+        dumps.append((np.load(tmp_path / run / "fwht_rows.npy"), np.load(tmp_path / run / "fwht_row_index.npy")))
+    (rows, idx), (rows_b, idx_b) = dumps
+    assert rows.dtype == np.float32 and idx.dtype == np.float64
+    assert np.array_equal(idx, np.arange(256)) and np.array_equal(idx, idx_b)
+    assert np.array_equal(rows.view(np.uint32), rows_b.view(np.uint32))
+    want = (torch.randn(256, 64, generator=torch.Generator().manual_seed(1234)) * 2.0 ** -15).numpy()   # bench.py's input
+    for _ in range(5):
+        want = oracle.fwht(want)
+    assert np.array_equal(rows.view(np.uint32), want.view(np.uint32))
+
+
 def test_bench_plain_command_starts_its_own_ranks(tmp_path):
     """``python bench.py --gpus 2`` as typed -- no launcher, no WORLD_SIZE: bench.py starts the two ranks itself as child
     processes (torch.distributed.run), passes rank 0's ONE JSON line through and exits with the children's code.  The
