@@ -337,6 +337,33 @@ int whvi_small_k_apply_f32(void *out, const void *x, const void *w, const void *
 int whvi_row_dot_f32(void *y, const void *x, const void *w, const void *bias, int64_t S, int64_t B, int32_t log2d,
                      int32_t flags, void *stream);
 
+/* The predictive pass of a WHVI regression network of the canonical shape -- WHVILinear(n_in, D), 1 .. 4 square
+ * WHVILinear(D, D), WHVILinear(D, 1), an optional ReLU at every boundary -- for all Monte-Carlo samples in ONE launch that
+ * keeps each row's hidden vector on chip (reads x, writes y; no (S, B, D) activation).  f32; per (s, b):
+ *     h = first(x[b, :]; s) (+ b_in) (relu if bit 0 of relu)
+ *     h = poison(h) * diag_m(s) + 0 (+ b_mid[m] if bit m of mid_bias) (relu if bit 1 + m of relu)    m = 0 .. n_mid - 1
+ *     y[s, b] = row_dot(h, w_out[s]) (+ b_out[0])
+ * with every stage the arithmetic of the launch it replaces, in the same order -- bit-identical to whvi_small_k_apply_f32 /
+ * x * w, whvi_diag_apply_f32 (WHVI_DIAG_MEAN_PLUS) and whvi_row_dot_f32 in sequence:
+ *   first = WHVI_MLP_FIRST_K4 / _K8 : x (B, K), w_in (S, D, K): fused multiply-adds in ascending c from +0 (stacked layer);
+ *   first = WHVI_MLP_FIRST_COLUMN   : x (B, 1), w_in (S, D): the plain product x[b, 0] * w_in[s, n] (column layer);
+ *   square layer m : s1, s2, b_mid (n_mid, D) rows m, u (n_mid, 1 + S, D) row block m -- mean row first, as whvi_diag_apply;
+ *                    a row holding a non-finite value turns its other entries into NaN first (the dense product's rule);
+ *   w_out (S, D), b_out one float or NULL; b_in D floats or NULL; b_mid may be NULL when mid_bias = 0.  A zero-filled bias
+ *   is NOT the same as none: the add turns -0 into +0.
+ * y (S, B) must not overlap any input; every pointer 16-byte aligned.  Supported: log2d in [6, 11], n_mid in [1, 4] and
+ * the operands of one sample in 64 KiB of LDS: 4 * 2^log2d * (K + 2 + 2 n_mid) <= 65536 bytes (K = 1 for the column layer)
+ * -- whvi_mlp_apply_supported(first, n_mid, log2d) returns 1 exactly then; otherwise the call returns WHVI_ERR_SIZE.
+ * No allocation, no synchronisation: capture-safe. */
+#define WHVI_MLP_FIRST_COLUMN 1
+#define WHVI_MLP_FIRST_K4     4
+#define WHVI_MLP_FIRST_K8     8
+int whvi_mlp_apply_supported(int32_t first, int32_t n_mid, int32_t log2d);
+int whvi_mlp_apply_f32(void *y, const void *x, int32_t first, const void *w_in, const void *b_in, int32_t n_mid,
+                       const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
+                       const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t relu,
+                       void *stream);
+
 /* whvi_reparam_kl_f32 with the eps draw inside the kernel: Philox4x32-10 + Box-Muller, one standard
  * normal per (matrix, sample, element), written to eps_out (J, S, D) for the backward pass / inspection.  The
  * generator state is three 64-bit words in DEVICE memory, state = {seed, launch offset, scratch (must be 0)}; the

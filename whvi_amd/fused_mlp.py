@@ -1,0 +1,159 @@
+"""One-launch predictive pass of a WHVI regression network of the canonical shape (opt-in:
+``WHVINetwork.set_fused_inference()``).
+
+The reference's network -- ``[WHVILinear(n_in, D), ReLU, WHVILinear(D, D), ReLU, WHVILinear(D, 1)]`` (src/evaluation.py:79-85,
+the toy notebook's 1 -> 128 -> 128 -> 1, BASELINE config 4's 3 -> 1024 -> 1024 -> 1) -- runs on the batched GPU route as three
+launches that write and re-read two ``(S, B, D)`` activations.  ``whvi_mlp_apply_f32`` (whvi_amd/csrc/mlp_apply.hpp) keeps
+each row's hidden vector on chip instead: it reads ``x`` and writes ``y``.  Every layer's operands come from the same
+``_mc_operands`` the batched route's ``forward_mc`` calls, in the same order, so the draws are the same; the kernel repeats
+the arithmetic of the launches it replaces, so the result is bit-identical to ``forward_batched`` without the flag.
+
+``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples)`` adds the checks of one call, ``run``
+makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the
+caller then takes the batched route.  There is no backward: a pass that needs an autograd graph takes the batched route."""
+from typing import List, NamedTuple, Optional, Union
+
+import torch
+import torch.nn as nn
+
+from whvi_amd import _hip
+from whvi_amd.layers import WHVILinear
+from whvi_amd.weights import WHVIColumnMatrix, WHVISquarePow2Matrix, WHVIStackedMatrix
+
+__all__ = ["Plan", "match", "plan", "run"]
+
+
+class Plan(NamedTuple):
+    first: nn.Module                 # WHVIStackedMatrix (K = D_in = 4 / 8) or WHVIColumnMatrix (n_in = 1)
+    kind: int                        # _hip.MLP_FIRST_K4 / _K8 / _COLUMN
+    n_in: int
+    mids: List[nn.Module]            # WHVISquarePow2Matrix, 1 .. 4 of them
+    last: nn.Module                  # transposed WHVIColumnMatrix (D -> 1)
+    layers: List[nn.Module]          # the WHVILinear modules in order (their _mc_kl is cleared like forward_batched does)
+    D: int
+    relu: int                        # bit 0: ReLU behind the first layer, bit 1 + m: behind square layer m
+
+
+def match(net) -> Union[Plan, str]:
+    """The plan of the one-launch pass for ``net``'s module list, or why it has none."""
+    mods = list(net.sequential)
+    layers, relu_after = [], []
+    for i, m in enumerate(mods):
+        if type(m) is nn.ReLU:
+            if not layers or relu_after[-1] or i == len(mods) - 1:
+                return f"module {i}: an nn.ReLU is only fused between two WHVI layers (one per boundary)"
+            relu_after[-1] = True
+        elif isinstance(m, WHVILinear):
+            layers.append(m)
+            relu_after.append(False)
+        else:
+            return f"module {i}: {type(m).__name__} is neither WHVILinear nor nn.ReLU"
+    if len(layers) < 3:
+        return f"{len(layers)} WHVI layers: the fused pass needs a first layer, 1 .. 4 square layers and an output layer"
+    if len(layers) - 2 > 4:
+        return f"{len(layers) - 2} square layers: at most 4"
+    subs = [m.weight_submodule for m in layers]
+    for i, w in enumerate(subs):
+        if not isinstance(w, (WHVIStackedMatrix, WHVIColumnMatrix, WHVISquarePow2Matrix)):
+            return f"layer {i}: {type(w).__name__} (mode='fastfood'?) is not a reference-mode WHVI matrix"
+        if getattr(w, "hip_apply", True) is False:
+            return f"layer {i}: faithful dataflow is on (hip_apply = False)"
+    first, mids, last = subs[0], subs[1:-1], subs[-1]
+    if isinstance(first, WHVIStackedMatrix):
+        if first.D_in not in (4, 8):
+            return f"first layer: {first.n_in} inputs pad to K = {first.D_in} (4 or 8 only)"
+        D, kind, n_in = first.n_out, first.D_in, first.n_in
+        if first.D_out != D:
+            return f"first layer: {D} outputs are not a whole number of {first.D_in}-row blocks"
+    elif isinstance(first, WHVIColumnMatrix) and not first.transposed:
+        D, kind, n_in = first.D, _hip.MLP_FIRST_COLUMN, 1
+        if first.D_adjusted != D:
+            return f"first layer: hidden width {D} is not a power of two"
+    else:
+        return f"first layer: {type(first).__name__} is neither a stacked (K = 4 / 8) nor a column (n_in = 1) WHVI matrix"
+    for j, w in enumerate(mids):
+        if not isinstance(w, WHVISquarePow2Matrix):
+            return f"layer {1 + j}: {type(w).__name__} is not a square power-of-two WHVI matrix (hidden width {D}?)"
+        if w.D != D:
+            return f"layer {1 + j}: width {w.D} differs from the first layer's {D}"
+        if w._diag_mode() is False:
+            return f"layer {1 + j}: faithful dataflow is on (the diagonal route is switched off)"
+    if not (isinstance(last, WHVIColumnMatrix) and last.transposed):
+        return f"output layer: {type(last).__name__} is not WHVILinear(D, 1) (one output only)"
+    if last.D != D or last.weight_submodule.D != D:
+        return f"output layer: width {last.D} differs from the hidden width {D}"
+    if not _hip.mlp_apply_supported(kind, len(mids), D):
+        return f"hidden width {D} with {len(mids)} square layers is outside whvi_mlp_apply's range"
+    relu = 0
+    for i, r in enumerate(relu_after[:-1]):
+        relu |= (1 << i) if r else 0
+    return Plan(first, kind, n_in, mids, last, layers, D, relu)
+
+
+def _params(p: Plan):
+    return [t for m in p.layers for t in m.parameters()]
+
+
+def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
+    """``match(net)`` plus the checks of this call: float32 CUDA input and parameters on x's device, sizes, and no autograd
+    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad)."""
+    p = match(net)
+    if isinstance(p, str):
+        return p
+    if x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != p.n_in:
+        return f"input: needs a float32 CUDA (batch, {p.n_in}) tensor"
+    params = _params(p)
+    if any(t.device != x.device or t.dtype != torch.float32 for t in params):
+        return "parameters: float32 on the input's device only"
+    S, B = int(n_samples), x.shape[0]
+    if S < 1 or S * B >= 2 ** 32:
+        return f"{S} samples x {B} rows: outside 1 .. 2^32 - 1 rows"
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
+        return "an autograd graph is wanted (the fused pass has no backward)"
+    return p
+
+
+def _bias(w) -> Optional[torch.Tensor]:
+    return None if w.bias is None else w.bias.reshape(-1)
+
+
+def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
+    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch.
+    Returns ``(batch, 1, S)`` in forward_batched's layout; sets ``net._pass_kl`` like the batched route does."""
+    S = int(n_samples)
+    first = p.first
+    w_in, kl = first._mc_operands(S)                                # (S, D, K) or (S, D)
+    kls = [kl]
+    if p.kind == _hip.MLP_FIRST_COLUMN:
+        xin = x
+    else:
+        xin = torch.zeros((x.shape[0], first.D_in), device=x.device)   # forward_mc's x_padded
+        xin[:, :first.n_in] = x
+    us = []
+    for w in p.mids:
+        u, kl = w._mc_operands(S)                                   # (1 + S, D)
+        us.append(u)
+        kls.append(kl)
+    w_out, kl = p.last._mc_operands(S)                              # (S, D)
+    kls.append(kl)
+    for m in p.layers:
+        m._mc_kl = None
+        m.weight_submodule._mc_kl = None
+    if len(p.mids) == 1:
+        m0 = p.mids[0]
+        s1, s2, u = m0.s1.unsqueeze(0), m0.s2.unsqueeze(0), us[0].unsqueeze(0)
+    else:
+        s1 = torch.stack([m.s1 for m in p.mids])
+        s2 = torch.stack([m.s2 for m in p.mids])
+        u = torch.stack(us)
+    mid_bias = sum(1 << j for j, m in enumerate(p.mids) if m.bias is not None)
+    b_mid = None
+    if mid_bias:
+        b_mid = torch.stack([m.bias.reshape(-1) if m.bias is not None else torch.zeros_like(m.s1) for m in p.mids])
+    y = _hip.mlp_apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias=mid_bias, relu=p.relu)
+    total = None
+    if all(torch.is_tensor(k) for k in kls):
+        for k in kls:
+            total = k if total is None else total + k
+    net._pass_kl = total
+    return y.unsqueeze(-1).permute(1, 2, 0)

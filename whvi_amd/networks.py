@@ -2,6 +2,7 @@
 ELBO, the two-phase training loop and evaluation.  Consumers of ``WHVILinear``; kept
 interface- and checkpoint-compatible (state_dict keys ``sequential.{i}....`` and
 ``likelihood.sigma``)."""
+import contextlib
 import pathlib
 from typing import Iterable, Tuple
 
@@ -47,6 +48,9 @@ class WHVINetwork(nn.Module, WHVI):
         # batched GEMM per layer); "auto" = batched on the GPU, loop on the host.
         self.mc_mode = "auto"
 
+    # opt-in (set_fused_inference): the batched predictive pass of a network of the canonical shape as ONE launch
+    fused_inference = False
+
     @property
     def kl(self):
         return sum([m.kl for m in self.sequential.children() if 'kl' in dir(m)])
@@ -83,6 +87,16 @@ class WHVINetwork(nn.Module, WHVI):
                 module._rng_state = None
         return self
 
+    def set_fused_inference(self, on: bool = True):
+        """Opt in to the one-launch predictive pass (``whvi_amd.fused_mlp``, ``whvi_mlp_apply_f32``) for networks of the
+        reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4 ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, ``nn.ReLU`` between
+        them or not; n_in <= 8.  ``forward_batched`` then makes the same draws in the same order and computes the same values
+        (bit for bit) without materialising the ``(S, batch, D)`` activations, whenever no autograd graph is wanted (grad mode
+        off, or nothing of the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before.
+        ``eval_model`` evaluates under ``torch.no_grad()`` while the flag is on."""
+        self.fused_inference = bool(on)
+        return self
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """(batch, in_dim) -> (batch, out_dim, n_samples): one stochastic pass per Monte-Carlo
         sample, samples stacked on the last axis (src/networks.py:36-54)."""
@@ -106,6 +120,11 @@ class WHVINetwork(nn.Module, WHVI):
         """All Monte-Carlo samples in one pass.  Activations carry a leading sample
         axis ``(S, batch, features)`` from the first WHVI layer on; deterministic modules broadcast
         over it.  Same output layout as the loop: ``(batch, out_dim, n_samples)``."""
+        if self.fused_inference:
+            from whvi_amd import fused_mlp
+            plan = fused_mlp.plan(self, x, n_samples)
+            if not isinstance(plan, str):
+                return fused_mlp.run(self, plan, x, n_samples)
         h = x
         fused_kl, complete = None, True
         modules = list(self.sequential)
@@ -289,9 +308,10 @@ class WHVINetwork(nn.Module, WHVI):
     def eval_model(self, X_test, y_test, loss) -> Tuple[float, float]:
         """(test error, test MNLL) with ``eval_samples`` draws (src/networks.py:101-115)."""
         self.eval()
-        y_pred = self(X_test)
-        test_mnll = self.likelihood.mnll_batch_estimate(y_test, y_pred, n=y_test.size(0))
-        return float(loss(y_pred, y_test).detach()), float(test_mnll.detach())
+        with torch.no_grad() if self.fused_inference else contextlib.nullcontext():   # the fused pass has no backward
+            y_pred = self(X_test)
+            test_mnll = self.likelihood.mnll_batch_estimate(y_test, y_pred, n=y_test.size(0))
+            return float(loss(y_pred, y_test).detach()), float(test_mnll.detach())
 
 
 def _fuses_relu(module, h):

@@ -537,6 +537,13 @@ class WHVISquarePow2Matrix(nn.Module):
             return self._diag_kernel(x, g_tilde.unsqueeze(0), self.bias, None, False)
         return F.linear(x, self.sample(), self.bias)
 
+    def _mc_operands(self, n_samples):
+        """(u (1 + S, D), KL of this pass or None): the draws of one batched pass -- one randn(S, D) draw (or the in-kernel
+        generator), softplus, g_sigma * eps and the KL terms; row 0 is g_mu, row 1 + k sample k's g_sigma * eps_k.  Shared by
+        ``forward_mc`` and the one-launch predictive pass (``whvi_amd.fused_mlp``), so that both consume the same stream."""
+        u, kl = _draw_and_reparam(self, self.g_mu.unsqueeze(0), self.g_rho.unsqueeze(0), n_samples, self.lambda_)
+        return u.squeeze(0), (None if kl is None else kl.squeeze(0))
+
     def forward_mc(self, x, n_samples, relu_in=False, relu_out=False):
         """``n_samples`` independent forward passes in one go: ``x`` is ``(batch, D)``
         (shared input) or ``(n_samples, batch, D)``; returns ``(n_samples, batch, D)``.  Sample k is
@@ -548,10 +555,7 @@ class WHVISquarePow2Matrix(nn.Module):
         if (relu_in or relu_out) and not self.fuses_relu(x):
             out = self.forward_mc(torch.relu(x) if relu_in else x, n_samples)
             return torch.relu(out) if relu_out else out
-        # one randn(S, D) draw (or the in-kernel generator), softplus, g_sigma * eps and the KL terms
-        u, kl = _draw_and_reparam(self, self.g_mu.unsqueeze(0), self.g_rho.unsqueeze(0), n_samples, self.lambda_)
-        u = u.squeeze(0)                                                          # (1 + S, D)
-        self._mc_kl = None if kl is None else kl.squeeze(0)   # KL of this pass, for WHVINetwork.loss
+        u, self._mc_kl = self._mc_operands(n_samples)   # KL of this pass, for WHVINetwork.loss
         route = self._diag_route(x)
         if route == "kernel":
             return self._diag_kernel(x, u, self.bias, n_samples, True, relu_in, relu_out)   # (S, batch, D), bias included
@@ -745,6 +749,22 @@ class WHVIStackedMatrix(nn.Module):
         return bool(self.hip_apply and x.dim() == 2 and x.device.type == "cuda" and x.dtype == torch.float32
                     and self.D_in in (4, 8) and _hip.small_k_apply_supported(x.new_empty((1, self.D_in)), self.stack * self.D_in))
 
+    def _mc_operands(self, n_samples):
+        """(W (S, stack * D_in, D_in), KL of this pass or None): every sample's stacked weight of one batched pass (the draws
+        of ``forward_mc``; shared with the one-launch predictive pass, ``whvi_amd.fused_mlp``)."""
+        S, J, D = n_samples, self.stack, self.D_in
+        dev = self._stacked_device()
+        s1, s2 = self._stacked("s1"), self._stacked("s2")
+        g_mu, g_rho = self._stacked("g_mu"), self._stacked("g_rho")
+        u, kl = _draw_and_reparam(self, g_mu, g_rho, S, self.lambda_)               # (J, 1 + S, D)
+        kl = None if kl is None else kl.sum()
+        if dev.type == "cuda":
+            W = WBarFunction.apply(s1, u, s2, None, True)                           # (J, S, D, D), the sum in-kernel
+        else:
+            W = torch.stack([torch.stack([m.w_bar(row) for row in u[j]]) for j, m in enumerate(self.weight_matrices)])
+            W = _mean_plus_rest(W, 1)
+        return W.transpose(0, 1).reshape(S, J * D, D), kl
+
     def forward_mc(self, x, n_samples, relu_in=False, relu_out=False):
         """Batched MC forward, see WHVISquarePow2Matrix.forward_mc; ``x``: (batch, n_in) or
         (n_samples, batch, n_in) -> (n_samples, batch, n_out).  Sample k of sub-matrix j uses row
@@ -753,22 +773,12 @@ class WHVIStackedMatrix(nn.Module):
             x = torch.relu(x)
         if relu_out and not self.fuses_relu(x):
             return torch.relu(self.forward_mc(x, n_samples))
-        S, J, D = n_samples, self.stack, self.D_in
-        dev = self._stacked_device()
-        s1, s2 = self._stacked("s1"), self._stacked("s2")
-        g_mu, g_rho = self._stacked("g_mu"), self._stacked("g_rho")
-        u, kl = _draw_and_reparam(self, g_mu, g_rho, S, self.lambda_)               # (J, 1 + S, D)
-        self._mc_kl = None if kl is None else kl.sum()
-        if dev.type == "cuda":
-            W = WBarFunction.apply(s1, u, s2, None, True)                           # (J, S, D, D), the sum in-kernel
-        else:
-            W = torch.stack([torch.stack([m.w_bar(row) for row in u[j]]) for j, m in enumerate(self.weight_matrices)])
-            W = _mean_plus_rest(W, 1)
-        W = W.transpose(0, 1).reshape(S, J * D, D)                                  # (S, stack*D, D)
+        D = self.D_in
+        W, self._mc_kl = self._mc_operands(n_samples)                              # (S, stack*D, D)
         x_padded = torch.zeros((*x.size()[:-1], D), device=x.device)
         x_padded[..., :self.n_in] = x
         from whvi_amd import _hip
-        if self.hip_apply and _hip.small_k_apply_supported(x_padded, J * D):
+        if self.hip_apply and _hip.small_k_apply_supported(x_padded, W.shape[1]):
             out = SmallKApplyFunction.apply(x_padded, W, self.bias, relu_out)       # one write-only launch (K = D_in = 4 or 8), bias (and ReLU) included
         else:
             out = torch.matmul(x_padded, W.transpose(1, 2))
@@ -826,6 +836,18 @@ class WHVIColumnMatrix(nn.Module):
         from whvi_amd import _hip
         return bool(self.hip_apply and self.transposed and x.dim() == 3 and self.D == self.weight_submodule.D and _hip.row_dot_supported(x))
 
+    def _mc_operands(self, n_samples):
+        """(w (S, D), KL of this pass or None): the first D entries of every sample's square matrix -- its row 0 -- for one
+        batched pass (the draws of ``forward_mc``; shared with the one-launch predictive pass, ``whvi_amd.fused_mlp``)."""
+        sq = self.weight_submodule
+        u, kl = _draw_and_reparam(self, sq.g_mu.unsqueeze(0), sq.g_rho.unsqueeze(0), n_samples, sq.lambda_)
+        g_tilde = _mean_plus_rest(u.squeeze(0), 0)                       # (S, D_adj): g_mu + g_sigma * eps
+        if g_tilde.device.type == "cuda":
+            rows0 = sq._w_bar_stack(g_tilde, rows=1).squeeze(1)          # (S, D_adj)
+        else:
+            rows0 = torch.stack([sq.w_bar(g)[0] for g in g_tilde])
+        return (rows0 if self.D == sq.D else rows0[:, :self.D]), (None if kl is None else kl.squeeze(0))
+
     def forward_mc(self, x, n_samples, relu_in=False, relu_out=False):
         """Batched MC forward (direct weight sampling like ``forward``); ``x``: (batch, n_in) or
         (n_samples, batch, n_in) -> (n_samples, batch, n_out).  Only row 0 of every sampled square
@@ -834,15 +856,7 @@ class WHVIColumnMatrix(nn.Module):
             return torch.relu(self.forward_mc(x, n_samples, relu_in=relu_in))
         if relu_in and not (self.fuses_relu(x) and x.shape[0] == n_samples):
             x, relu_in = torch.relu(x), False
-        sq = self.weight_submodule
-        u, kl = _draw_and_reparam(self, sq.g_mu.unsqueeze(0), sq.g_rho.unsqueeze(0), n_samples, sq.lambda_)
-        self._mc_kl = None if kl is None else kl.squeeze(0)
-        g_tilde = _mean_plus_rest(u.squeeze(0), 0)                       # (S, D_adj): g_mu + g_sigma * eps
-        if g_tilde.device.type == "cuda":
-            rows0 = sq._w_bar_stack(g_tilde, rows=1).squeeze(1)          # (S, D_adj)
-        else:
-            rows0 = torch.stack([sq.w_bar(g)[0] for g in g_tilde])
-        w = rows0 if self.D == sq.D else rows0[:, :self.D]               # (S, D)
+        w, self._mc_kl = self._mc_operands(n_samples)                   # (S, D)
         if self.transposed:                       # weight (1, D): out = F.linear(x, w[None]) per sample = x @ w: one read of x
             from whvi_amd import _hip
             if self.hip_apply and x.dim() == 3 and x.shape[0] == n_samples and _hip.row_dot_supported(x):
