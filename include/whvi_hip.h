@@ -364,6 +364,32 @@ int whvi_mlp_apply_f32(void *y, const void *x, int32_t first, const void *w_in, 
                        const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t relu,
                        void *stream);
 
+/* Backward of whvi_mlp_apply_f32: from g = dL/dy (S, B) and the forward's operands (same arguments; b_out is not needed), the
+ * gradients of every operand, without a saved activation.  Each row's hidden vectors are recomputed with the forward's
+ * arithmetic (same ReLU masks, same poisoned rows), then the three-launch route's backward formulas run element by element:
+ *     d = g * w_out;  at square layer m (last first): d = 0 where its fused ReLU's pre-activation, recomputed from the layer's
+ *     input before the poison, has relu(z) <= 0 (NaN passes);  d = d * diag_m;  behind the first layer: d = 0 where h <= 0
+ *     (column layer; NaN passes) or d = d * (h > 0) (stacked layer).
+ *   grad_w_in  : (S, D, K) = sum_b d x[b, c]   (column layer: (S, D))
+ *   grad_w_mid : (n_mid, S, D) = sum_b d_m h_{m-1}, the gradient w.r.t. each sample's diagonal (chain it to s1, s2, u as
+ *                whvi_diag_apply_bwd's slots do)
+ *   grad_w_out : (S, D) = sum_b g h_L
+ *   grad_b     : (1 + n_mid) D + 1 floats: b_in (D), b_mid (n_mid rows of D), b_out (1), summed over samples and rows --
+ *                written whatever the forward's bias pointers were
+ *   grad_x     : (S, B, K) (column layer: (S, B, 1)) = sum_n d w_in[s, n, c], or NULL to skip; the caller sums over S
+ *   work       : workspace of work_floats >= whvi_mlp_apply_bwd_workspace(S, B, first, n_mid, log2d) floats (WHVI_ERR_ARG
+ *                otherwise).  Every block writes its partial sums there and a second, tiny launch inside the same call adds
+ *                them in ascending slab and sample order: deterministic (bit-identical on every run), no atomics.
+ * Supported: whvi_mlp_apply_supported's range with n_mid <= 2 and log2d <= 10 -- whvi_mlp_apply_bwd_supported(first, n_mid,
+ * log2d) returns 1 exactly then, whvi_mlp_apply_bwd_workspace returns -1 otherwise.  Every argument check runs before any
+ * launch.  No allocation, no synchronisation: capture-safe. */
+int whvi_mlp_apply_bwd_supported(int32_t first, int32_t n_mid, int32_t log2d);
+int64_t whvi_mlp_apply_bwd_workspace(int64_t S, int64_t B, int32_t first, int32_t n_mid, int32_t log2d);
+int whvi_mlp_apply_bwd_f32(void *grad_w_in, void *grad_w_mid, void *grad_w_out, void *grad_b, void *grad_x, void *work,
+                           int64_t work_floats, const void *g, const void *x, int32_t first, const void *w_in, const void *b_in,
+                           int32_t n_mid, const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
+                           const void *w_out, int64_t S, int64_t B, int32_t log2d, int32_t relu, void *stream);
+
 /* whvi_reparam_kl_f32 with the eps draw inside the kernel: Philox4x32-10 + Box-Muller, one standard
  * normal per (matrix, sample, element), written to eps_out (J, S, D) for the backward pass / inspection.  The
  * generator state is three 64-bit words in DEVICE memory, state = {seed, launch offset, scratch (must be 0)}; the

@@ -68,29 +68,18 @@ __device__ __forceinline__ void mlp_poison_rows(float (&h)[R][C][4])
     }
 }
 
-// y[s, b] for b in the block's slab.  x : (B, KIN); w_in : (S, D, KIN) (KIN = 4 / 8) or (S, D) (KIN = 1); s1, s2, b_mid :
-// (n_mid, D); u : (n_mid, 1 + S, D) (mean row first, whvi_diag_apply's WHVI_DIAG_MEAN_PLUS layout); w_out : (S, D).
-// relu bit 0: behind the first layer, bit 1 + m: behind square layer m.  mid_bias bit m: square layer m has a bias.
-template <typename T, int LOG2D, int KIN>      // (T = float; named so that whvi_last_kernel prints the real symbol)
-__global__ void __launch_bounds__(256)
-mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ w_in, const float *__restrict__ b_in,
-                 const float *__restrict__ s1, const float *__restrict__ s2, const float *__restrict__ u,
-                 const float *__restrict__ b_mid, const float *__restrict__ w_out, const float *__restrict__ b_out, uint32_t S,
-                 uint32_t B, uint32_t n_mid, uint32_t mid_bias, uint32_t relu, uint32_t slab_rows, uint32_t n_slabs)
+// This sample's operands into the block's LDS: W1 transposed to [c][n], b_in, per square layer its diagonal and bias, w_out.
+// (Shared with the backward, mlp_apply_bwd.hpp, which recomputes the hidden vectors from the same copies.)
+template <int LOG2D, int KIN>
+__device__ __forceinline__ void mlp_stage_operands(float *lds, uint32_t s, const float *__restrict__ w_in,
+                                                   const float *__restrict__ b_in, const float *__restrict__ s1,
+                                                   const float *__restrict__ s2, const float *__restrict__ u,
+                                                   const float *__restrict__ b_mid, const float *__restrict__ w_out,
+                                                   uint32_t S, uint32_t n_mid, uint32_t mid_bias)
 {
-    using Gm = MlpGeom<LOG2D>;
-    constexpr int D = Gm::D, L = Gm::L, C = Gm::C, R = Gm::R, RPI = Gm::RPI;
+    constexpr int D = 1 << LOG2D;
     typedef float f4 __attribute__((ext_vector_type(4)));
-    extern __shared__ __attribute__((aligned(16))) float mlp_lds[];
-    float *lw1 = mlp_lds;                    // [c][n]: KIN rows of D
-    float *lbi = lw1 + KIN * D;              // b_in
-    float *lmid = lbi + D;                   // square layer m: diagonal at 2 m D, bias at (2 m + 1) D
-    float *lwo = lmid + 2 * n_mid * D;       // w_out
-
-    const uint32_t s = blockIdx.x / n_slabs, slab = blockIdx.x - s * n_slabs;
-    const uint32_t b0 = slab * slab_rows, b1 = b0 + slab_rows < B ? b0 + slab_rows : B;
-
-    // ---- this sample's operands into LDS
+    float *lw1 = lds, *lbi = lw1 + KIN * D, *lmid = lbi + D, *lwo = lmid + 2 * n_mid * D;
     for (uint32_t n = threadIdx.x; n < (uint32_t)D; n += 256) {
         if constexpr (KIN == 1) {
             lw1[n] = w_in[(size_t)s * D + n];
@@ -114,6 +103,148 @@ mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float
                 ((mid_bias >> m) & 1u) ? reinterpret_cast<const f4 *>(b_mid + (size_t)m * D)[c] : f4{0.f, 0.f, 0.f, 0.f};
         }
     }
+}
+
+// x[row, :] of the R rows r0 .. r0 + R - 1 (rows past b1 read row b1 - 1: valid operands, never stored)
+template <int KIN, int R>
+__device__ __forceinline__ void mlp_load_x(float (&xv)[R][KIN], const float *__restrict__ x, uint32_t r0, uint32_t b1)
+{
+    typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const uint32_t row = r0 + r < b1 ? r0 + r : b1 - 1;
+        if constexpr (KIN == 1) {
+            xv[r][0] = x[row];
+        } else {
+#pragma unroll
+            for (int g = 0; g < KIN / 4; ++g) {
+                const f4 v = reinterpret_cast<const f4 *>(x + (size_t)row * KIN)[g];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) xv[r][4 * g + e] = v[e];
+            }
+        }
+    }
+}
+
+// first layer: small_k_apply_kernel's +0-initialised fmaf chain (KIN = 4 / 8) or the column layer's plain product, + b_in, relu_
+template <int LOG2D, int KIN, int R>
+__device__ __forceinline__ void mlp_first_layer(float (&h)[R][MlpGeom<LOG2D>::C][4], const float (&xv)[R][KIN], const float *lw1,
+                                                const float *lbi, uint32_t col, bool has_b_in, bool relu0)
+{
+    using Gm = MlpGeom<LOG2D>;
+    constexpr int D = Gm::D, L = Gm::L, C = Gm::C;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const uint32_t q = col + j * L;
+        f4 wc[KIN];
+#pragma unroll
+        for (int c = 0; c < KIN; ++c) wc[c] = reinterpret_cast<const f4 *>(lw1 + c * D)[q];
+        const f4 bc = reinterpret_cast<const f4 *>(lbi)[q];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float a;
+                if constexpr (KIN == 1) {
+                    a = xv[r][0] * wc[0][e];                       // `x * w`: one rounding, no accumulator
+                } else {
+                    a = 0.0f;                                      // the GEMM's +0-initialised accumulator
+#pragma unroll
+                    for (int c = 0; c < KIN; ++c) a = __builtin_fmaf(xv[r][c], wc[c][e], a);
+                }
+                if (has_b_in) a = a + bc[e];
+                if (relu0) a = relu_(a);
+                h[r][j][e] = a;
+            }
+    }
+}
+
+// one square layer in place: diag_apply_kernel's row poison, r * wbar_diag + 0, + bias, relu_.  lw: the layer's diagonal,
+// lb: its bias (LDS).  MASK (the backward): bit (r C + j) 4 + e of *mask = the fused ReLU's gradient passes there, as
+// whvi_diag_apply_bwd recomputes it -- from the layer's input BEFORE the poison: !(relu_(h * w (+ b)) <= 0), NaN passes
+template <int LOG2D, int R, bool MASK = false>
+__device__ __forceinline__ void mlp_square_layer(float (&h)[R][MlpGeom<LOG2D>::C][4], const float *lw, const float *lb,
+                                                 uint32_t col, bool hb, bool hr, uint32_t *mask = nullptr)
+{
+    using Gm = MlpGeom<LOG2D>;
+    constexpr int L = Gm::L, C = Gm::C;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    bool bad = false;
+#pragma unroll
+    for (int r = 0; r < R; ++r)
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) bad |= !__builtin_isfinite(h[r][j][e]);
+    const bool poison = __builtin_amdgcn_ballot_w64(bad) != 0;
+    if (poison) {
+        if constexpr (MASK) {
+            uint32_t mk = 0;
+#pragma unroll
+            for (int j = 0; j < C; ++j) {
+                const f4 wc = reinterpret_cast<const f4 *>(lw)[col + j * L];
+                const f4 bc = reinterpret_cast<const f4 *>(lb)[col + j * L];
+#pragma unroll
+                for (int r = 0; r < R; ++r)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float z = h[r][j][e] * wc[e];
+                        if (hb) z = z + bc[e];
+                        if (!(relu_(z) <= 0.0f)) mk |= 1u << ((r * C + j) * 4 + e);
+                    }
+            }
+            *mask = mk;
+        }
+        mlp_poison_rows<L, R, C>(h);
+    }
+    uint32_t mk = 0;
+#pragma unroll
+    for (int j = 0; j < C; ++j) {
+        const uint32_t q = col + j * L;
+        const f4 wc = reinterpret_cast<const f4 *>(lw)[q];
+        const f4 bc = reinterpret_cast<const f4 *>(lb)[q];
+#pragma unroll
+        for (int r = 0; r < R; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float v = h[r][j][e] * wc[e] + 0.0f;               // the one non-zero product + the accumulator's +0
+                if (hb) v = v + bc[e];
+                if constexpr (MASK) {
+                    if (!(relu_(v) <= 0.0f)) mk |= 1u << ((r * C + j) * 4 + e);
+                }
+                if (hr) v = relu_(v);
+                h[r][j][e] = v;
+            }
+    }
+    if constexpr (MASK) {
+        if (!poison) *mask = mk;
+    }
+}
+
+// y[s, b] for b in the block's slab.  x : (B, KIN); w_in : (S, D, KIN) (KIN = 4 / 8) or (S, D) (KIN = 1); s1, s2, b_mid :
+// (n_mid, D); u : (n_mid, 1 + S, D) (mean row first, whvi_diag_apply's WHVI_DIAG_MEAN_PLUS layout); w_out : (S, D).
+// relu bit 0: behind the first layer, bit 1 + m: behind square layer m.  mid_bias bit m: square layer m has a bias.
+template <typename T, int LOG2D, int KIN>      // (T = float; named so that whvi_last_kernel prints the real symbol)
+__global__ void __launch_bounds__(256)
+mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ w_in, const float *__restrict__ b_in,
+                 const float *__restrict__ s1, const float *__restrict__ s2, const float *__restrict__ u,
+                 const float *__restrict__ b_mid, const float *__restrict__ w_out, const float *__restrict__ b_out, uint32_t S,
+                 uint32_t B, uint32_t n_mid, uint32_t mid_bias, uint32_t relu, uint32_t slab_rows, uint32_t n_slabs)
+{
+    using Gm = MlpGeom<LOG2D>;
+    constexpr int D = Gm::D, L = Gm::L, C = Gm::C, R = Gm::R, RPI = Gm::RPI;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) float mlp_lds[];
+    float *lw1 = mlp_lds;                    // [c][n]: KIN rows of D
+    float *lbi = lw1 + KIN * D;              // b_in
+    float *lmid = lbi + D;                   // square layer m: diagonal at 2 m D, bias at (2 m + 1) D
+    float *lwo = lmid + 2 * n_mid * D;       // w_out
+
+    const uint32_t s = blockIdx.x / n_slabs, slab = blockIdx.x - s * n_slabs;
+    const uint32_t b0 = slab * slab_rows, b1 = b0 + slab_rows < B ? b0 + slab_rows : B;
+
+    mlp_stage_operands<LOG2D, KIN>(mlp_lds, s, w_in, b_in, s1, s2, u, b_mid, w_out, S, n_mid, mid_bias);
     __syncthreads();
 
     const int lane = threadIdx.x & 63;
@@ -127,73 +258,12 @@ mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float
         float h[R][C][4];
         {   // ---- first layer
             float xv[R][KIN];
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const uint32_t row = r0 + r < b1 ? r0 + r : b1 - 1;
-                if constexpr (KIN == 1) {
-                    xv[r][0] = x[row];
-                } else {
-#pragma unroll
-                    for (int g = 0; g < KIN / 4; ++g) {
-                        const f4 v = reinterpret_cast<const f4 *>(x + (size_t)row * KIN)[g];
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) xv[r][4 * g + e] = v[e];
-                    }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < C; ++j) {
-                const uint32_t q = col + j * L;
-                f4 wc[KIN];
-#pragma unroll
-                for (int c = 0; c < KIN; ++c) wc[c] = reinterpret_cast<const f4 *>(lw1 + c * D)[q];
-                const f4 bc = reinterpret_cast<const f4 *>(lbi)[q];
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float a;
-                        if constexpr (KIN == 1) {
-                            a = xv[r][0] * wc[0][e];                       // `x * w`: one rounding, no accumulator
-                        } else {
-                            a = 0.0f;                                      // the GEMM's +0-initialised accumulator
-#pragma unroll
-                            for (int c = 0; c < KIN; ++c) a = __builtin_fmaf(xv[r][c], wc[c][e], a);
-                        }
-                        if (has_b_in) a = a + bc[e];
-                        if (relu & 1u) a = relu_(a);
-                        h[r][j][e] = a;
-                    }
-            }
+            mlp_load_x<KIN, R>(xv, x, r0, b1);
+            mlp_first_layer<LOG2D, KIN, R>(h, xv, lw1, lbi, col, has_b_in, (relu & 1u) != 0);
         }
         // ---- square layers
-        for (uint32_t m = 0; m < n_mid; ++m) {
-            bool bad = false;
-#pragma unroll
-            for (int r = 0; r < R; ++r)
-#pragma unroll
-                for (int j = 0; j < C; ++j)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) bad |= !__builtin_isfinite(h[r][j][e]);
-            if (__builtin_amdgcn_ballot_w64(bad) != 0) mlp_poison_rows<L, R, C>(h);
-            const float *lw = lmid + 2 * m * D, *lb = lw + D;
-            const bool hb = (mid_bias >> m) & 1u, hr = (relu >> (m + 1)) & 1u;
-#pragma unroll
-            for (int j = 0; j < C; ++j) {
-                const uint32_t q = col + j * L;
-                const f4 wc = reinterpret_cast<const f4 *>(lw)[q];
-                const f4 bc = reinterpret_cast<const f4 *>(lb)[q];
-#pragma unroll
-                for (int r = 0; r < R; ++r)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float v = h[r][j][e] * wc[e] + 0.0f;               // the one non-zero product + the accumulator's +0
-                        if (hb) v = v + bc[e];
-                        if (hr) v = relu_(v);
-                        h[r][j][e] = v;
-                    }
-            }
-        }
+        for (uint32_t m = 0; m < n_mid; ++m)
+            mlp_square_layer<LOG2D, R>(h, lmid + 2 * m * D, lmid + (2 * m + 1) * D, col, (mid_bias >> m) & 1u, (relu >> (m + 1)) & 1u);
         // ---- transposed column layer: row_dot_kernel's partials, order and butterfly
         float acc[R];
 #pragma unroll

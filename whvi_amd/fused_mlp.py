@@ -1,5 +1,5 @@
-"""One-launch predictive pass of a WHVI regression network of the canonical shape (opt-in:
-``WHVINetwork.set_fused_inference()``).
+"""One-launch passes of a WHVI regression network of the canonical shape: the predictive pass (opt-in:
+``WHVINetwork.set_fused_inference()``) and the training pass, forward + backward (opt-in: ``WHVINetwork.set_fused_training()``).
 
 The reference's network -- ``[WHVILinear(n_in, D), ReLU, WHVILinear(D, D), ReLU, WHVILinear(D, 1)]`` (src/evaluation.py:79-85,
 the toy notebook's 1 -> 128 -> 128 -> 1, BASELINE config 4's 3 -> 1024 -> 1024 -> 1) -- runs on the batched GPU route as three
@@ -8,9 +8,17 @@ each row's hidden vector on chip instead: it reads ``x`` and writes ``y``.  Ever
 ``_mc_operands`` the batched route's ``forward_mc`` calls, in the same order, so the draws are the same; the kernel repeats
 the arithmetic of the launches it replaces, so the result is bit-identical to ``forward_batched`` without the flag.
 
-``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples)`` adds the checks of one call, ``run``
-makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the
-caller then takes the batched route.  There is no backward: a pass that needs an autograd graph takes the batched route."""
+Training: ``MLPApplyFunction`` wraps the same launch in an autograd Function that saves only its inputs.  Its backward is
+one call of ``whvi_mlp_apply_bwd_f32`` (whvi_amd/csrc/mlp_apply_bwd.hpp), which recomputes every row's hidden vectors with the
+forward's arithmetic -- hence the batched route's ReLU masks -- and applies that route's backward formulas; the batch sums run
+in a fixed order (bit-identical gradients on every run).  They differ from the batched route's gradients only by summation
+order; the loss is bit-identical.  The gradient w.r.t. each square layer's diagonal is chained to ``u``, ``s1`` and ``s2`` by
+small torch ops, and autograd continues through ``_mc_operands`` to the parameters.  There is no double backward.
+
+``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples[, training])`` adds the checks of one call,
+``run`` makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the
+caller then takes the batched route.  The predictive plan (``training=False``) refuses a call that wants an autograd graph;
+the training plan (``training=True``) takes exactly those, within ``whvi_mlp_apply_bwd_f32``'s narrower range."""
 from typing import List, NamedTuple, Optional, Union
 
 import torch
@@ -20,7 +28,7 @@ from whvi_amd import _hip
 from whvi_amd.layers import WHVILinear
 from whvi_amd.weights import WHVIColumnMatrix, WHVISquarePow2Matrix, WHVIStackedMatrix
 
-__all__ = ["Plan", "match", "plan", "run"]
+__all__ = ["Plan", "MLPApplyFunction", "match", "plan", "run"]
 
 
 class Plan(NamedTuple):
@@ -94,9 +102,11 @@ def _params(p: Plan):
     return [t for m in p.layers for t in m.parameters()]
 
 
-def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
+def plan(net, x: torch.Tensor, n_samples: int, training: bool = False) -> Union[Plan, str]:
     """``match(net)`` plus the checks of this call: float32 CUDA input and parameters on x's device, sizes, and no autograd
-    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad)."""
+    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad).  ``training=True``: the plan of the
+    trainable pass instead -- the same checks, but a graph must be wanted and the network must lie in the backward's range
+    (``_hip.mlp_apply_bwd_supported``)."""
     p = match(net)
     if isinstance(p, str):
         return p
@@ -108,18 +118,64 @@ def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
     S, B = int(n_samples), x.shape[0]
     if S < 1 or S * B >= 2 ** 32:
         return f"{S} samples x {B} rows: outside 1 .. 2^32 - 1 rows"
-    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
-        return "an autograd graph is wanted (the fused pass has no backward)"
+    wanted = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params))
+    if not training:
+        return "an autograd graph is wanted (the fused pass has no backward)" if wanted else p
+    if not wanted:
+        return "no autograd graph is wanted (the training pass is for passes that need one)"
+    if not _hip.mlp_apply_bwd_supported(p.kind, len(p.mids), p.D):
+        return f"hidden width {p.D} with {len(p.mids)} square layers is outside whvi_mlp_apply_bwd's range"
     return p
+
+
+class MLPApplyFunction(torch.autograd.Function):
+    """``y (S, B) = mlp_apply(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out)`` (whvi_mlp_apply_f32) with a backward: one call of
+    ``whvi_mlp_apply_bwd_f32`` that recomputes the hidden vectors instead of reading saved ones (only the inputs are saved).
+    ``s1, s2`` (n_mid, D), ``u`` (n_mid, 1 + S, D) as ``whvi_diag_apply``'s mean-plus layout; the gradient w.r.t. each sample's
+    diagonal goes to ``u``, ``s1`` and ``s2`` with the formulas of ``whvi_diag_apply_bwd``'s finishing launch, row 0 of ``u``
+    (the mean) taking the sum over the samples, as ``DiagApplyFunction.backward`` does.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias, relu):
+        ctx.mid_bias, ctx.relu = int(mid_bias), int(relu)
+        ctx.save_for_backward(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out)
+        return _hip.mlp_apply(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias=mid_bias, relu=relu)
+
+    @staticmethod
+    def backward(ctx, g):
+        if torch.is_grad_enabled():
+            raise RuntimeError("MLPApplyFunction: the fused training pass has no double backward -- call backward() without "
+                               "create_graph=True, or turn WHVINetwork.set_fused_training off for this pass")
+        x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gw_in, gw_mid, gw_out, gb, gx = _hip.mlp_apply_bwd(g, x, w_in, b_in, s1, s2, u, b_mid, w_out, mid_bias=ctx.mid_bias,
+                                                          relu=ctx.relu, need_grad_x=need[0])
+        n_mid, S, D = gw_mid.shape
+        grad_x = gx.sum(dim=0) if gx is not None else None
+        grad_b_in = gb[:D].view(b_in.shape) if b_in is not None else None
+        grad_b_mid = gb[D:(1 + n_mid) * D].view(b_mid.shape) if b_mid is not None else None
+        grad_b_out = gb[(1 + n_mid) * D:].view(b_out.shape) if b_out is not None else None
+        grad_s1 = grad_s2 = grad_u = None
+        if need[3] or need[4] or need[5]:
+            # d w_k / d (s1, s2, u) of w_k = wbar(u_0) + wbar(u_1+k) = s1 * D * (u_0 * s2) + s1 * D * (u_1+k * s2), per sample k
+            Dd = float(D)
+            a, c = s1.unsqueeze(1), s2.unsqueeze(1)
+            u0, uk = u[:, :1], u[:, 1:]
+            k_u = gw_mid * (a * Dd * c)                                           # (n_mid, S, D): dL/du_1+k
+            grad_u = torch.cat((k_u.sum(dim=1, keepdim=True), k_u), dim=1)        # row 0 (the mean) takes the sum
+            grad_s1 = (gw_mid * (Dd * (u0 * c) + Dd * (uk * c))).sum(dim=1)
+            grad_s2 = (gw_mid * (a * Dd * (u0 + uk))).sum(dim=1)
+        return grad_x, gw_in, grad_b_in, grad_s1, grad_s2, grad_u, grad_b_mid, gw_out, grad_b_out, None, None
 
 
 def _bias(w) -> Optional[torch.Tensor]:
     return None if w.bias is None else w.bias.reshape(-1)
 
 
-def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
-    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch.
-    Returns ``(batch, 1, S)`` in forward_batched's layout; sets ``net._pass_kl`` like the batched route does."""
+def run(net, p: Plan, x: torch.Tensor, n_samples: int, training: bool = False) -> torch.Tensor:
+    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch
+    (``training``: through ``MLPApplyFunction``, for a plan of ``plan(..., training=True)``).  Returns ``(batch, 1, S)`` in
+    forward_batched's layout; sets ``net._pass_kl`` like the batched route does."""
     S = int(n_samples)
     first = p.first
     w_in, kl = first._mc_operands(S)                                # (S, D, K) or (S, D)
@@ -150,7 +206,10 @@ def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
     b_mid = None
     if mid_bias:
         b_mid = torch.stack([m.bias.reshape(-1) if m.bias is not None else torch.zeros_like(m.s1) for m in p.mids])
-    y = _hip.mlp_apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias=mid_bias, relu=p.relu)
+    if training:
+        y = MLPApplyFunction.apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias, p.relu)
+    else:
+        y = _hip.mlp_apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias=mid_bias, relu=p.relu)
     total = None
     if all(torch.is_tensor(k) for k in kls):
         for k in kls:

@@ -50,6 +50,8 @@ class WHVINetwork(nn.Module, WHVI):
 
     # opt-in (set_fused_inference): the batched predictive pass of a network of the canonical shape as ONE launch
     fused_inference = False
+    # opt-in (set_fused_training): the same network's grad-wanting pass as one forward + one backward launch
+    fused_training = False
 
     @property
     def kl(self):
@@ -92,9 +94,20 @@ class WHVINetwork(nn.Module, WHVI):
         reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4 ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, ``nn.ReLU`` between
         them or not; n_in <= 8.  ``forward_batched`` then makes the same draws in the same order and computes the same values
         (bit for bit) without materialising the ``(S, batch, D)`` activations, whenever no autograd graph is wanted (grad mode
-        off, or nothing of the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before.
-        ``eval_model`` evaluates under ``torch.no_grad()`` while the flag is on."""
+        off, or nothing of the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before
+        (a pass that wants a graph takes the fused route only with ``set_fused_training``).  ``eval_model`` evaluates under
+        ``torch.no_grad()`` while the flag is on."""
         self.fused_inference = bool(on)
+        return self
+
+    def set_fused_training(self, on: bool = True):
+        """Opt in to the trainable one-launch pass (``whvi_amd.fused_mlp.MLPApplyFunction``: ``whvi_mlp_apply_f32`` forward,
+        ``whvi_mlp_apply_bwd_f32`` backward) for the networks ``set_fused_inference`` covers, with at most 2 square layers and
+        D <= 1024.  A ``forward_batched`` call that wants an autograd graph then makes the same draws, returns the same values
+        (bit for bit) and saves no ``(S, batch, D)`` activation; its gradients differ from the batched route's only by
+        summation order, and are the same on every run.  No double backward (``create_graph=True`` raises).  Every other call
+        takes the route it takes without this flag; the two flags are independent."""
+        self.fused_training = bool(on)
         return self
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -125,6 +138,11 @@ class WHVINetwork(nn.Module, WHVI):
             plan = fused_mlp.plan(self, x, n_samples)
             if not isinstance(plan, str):
                 return fused_mlp.run(self, plan, x, n_samples)
+        if self.fused_training and torch.is_grad_enabled():
+            from whvi_amd import fused_mlp
+            plan = fused_mlp.plan(self, x, n_samples, training=True)
+            if not isinstance(plan, str):
+                return fused_mlp.run(self, plan, x, n_samples, training=True)
         h = x
         fused_kl, complete = None, True
         modules = list(self.sequential)
