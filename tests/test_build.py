@@ -135,3 +135,32 @@ def test_shipped_kernels_keep_their_occupancy_and_store_issue_form(tmp_path):
     with ShippedLibrary(str(obj)) as tuned:
         bad = _issue_violations(tuned, ISSUE_CONTRACTS[:1])
     assert len(bad) == 1 and "back to back" in bad[0], bad
+
+
+def test_no_store_data_hazard_in_the_shipped_library(tmp_path):
+    """A VALU write to the data VGPRs of a store wider than 64 bits needs two wait states behind the store on gfx950, or the
+    store may write the new value.  hipcc pads the stores it emits; an inline-asm store is one opaque statement to it, so the
+    instruction after it can land in the window -- whvi_diag_apply_bwd's long-stream grad_x store (diag_apply.hpp, st16_stream)
+    did, and wrote g * x instead of g * w into some elements of config 4's grad_x.  Every wide store of every shipped kernel
+    is checked.  The check is proven able to fail on a kernel with the unpadded pattern, and to accept it with its pad."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from shipped_isa import ShippedLibrary, store_data_hazards
+    with ShippedLibrary() as shipped:
+        pretty = {k["mangled"]: n for n, k in shipped.kernels.items()}
+        bad = [(pretty.get(sym, sym),) + rest for co in sorted({k["code_object"] for k in shipped.kernels.values()})
+               for sym, *rest in store_data_hazards(co)]
+    assert bad == [], bad[:8]
+    src = tmp_path / "hazard.hip"
+    found = []
+    for pad in ("", "\\n\\ts_nop 0", "\\n\\ts_nop 1"):
+        src.write_text('#include <hip/hip_runtime.h>\n'
+                       '__global__ void k(unsigned *p) {\n'
+                       '    asm volatile("global_store_dwordx4 %0, v[4:7], off' + pad + '\\n\\tv_mov_b32 v4, 0"'
+                       ' :: "v"(p + 4 * threadIdx.x) : "v4", "v5", "v6", "v7", "memory");\n}\n')
+        obj = tmp_path / "hazard.o"
+        build = subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-c", str(src), "-o", str(obj)],
+                               capture_output=True, text=True, timeout=600)
+        assert build.returncode == 0, build.stderr[-2000:]
+        with ShippedLibrary(str(obj)) as tiny:
+            found.append([w for co in {k["code_object"] for k in tiny.kernels.values()} for *_, w in store_data_hazards(co)])
+    assert found == [[0], [1], []], found

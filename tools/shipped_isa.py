@@ -96,6 +96,65 @@ def store_runs(ops, mnemonic):
     return runs
 
 
+_INSN = re.compile(r"^\s+([a-z_0-9]+)\s*(.*?)\s*//\s*([0-9A-F]+):")
+_SYMBOL = re.compile(r"^[0-9a-f]+ <(\S+)>:")
+_WIDE_STORE = re.compile(r"(global|flat|scratch|buffer)_store_(dwordx3|dwordx4|b96|b128)$")
+
+
+def _vgprs(operand):
+    m = re.fullmatch(r"v(\d+)", operand) or re.fullmatch(r"v\[(\d+):(\d+)\]", operand)
+    if not m:
+        return set()
+    return set(range(int(m.group(1)), int(m.group(m.lastindex)) + 1))
+
+
+def store_data_hazards(code_object, wait_states=2):
+    """Stores of more than 64 bits whose data VGPRs a VALU instruction overwrites fewer than ``wait_states`` wait states later
+    (every instruction is one, ``s_nop N`` is N + 1; branches are followed).  The hardware may then store the NEW value: gfx950
+    needs two wait states there.  hipcc pads the stores it emits; an inline-asm store has to carry its own ``s_nop``.
+    Returns [(mangled kernel, store, the VALU instruction, wait states between them)]."""
+    text = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", code_object], check=True, capture_output=True,
+                          text=True).stdout
+    ins, index, symbol = [], {}, None
+    for line in text.splitlines():
+        s = _SYMBOL.match(line)
+        if s:
+            symbol = s.group(1)
+            continue
+        m = _INSN.match(line)
+        if m:
+            index[int(m.group(3), 16)] = len(ins)
+            ins.append((m.group(1), m.group(2), int(m.group(3), 16), symbol))
+    found = []
+    for i, (op, args, _, symbol) in enumerate(ins):
+        if not _WIDE_STORE.match(op):
+            continue
+        operands = [t.strip() for t in re.split(r",\s*(?![^\[]*\])", args)]
+        data = _vgprs(operands[0] if op.startswith("buffer_") else operands[1])
+        todo, seen = [(i + 1, 0)], set()
+        while todo:
+            j, waited = todo.pop()
+            if j >= len(ins) or waited >= wait_states or (j, waited) in seen:
+                continue
+            seen.add((j, waited))
+            nop, nargs, addr, _ = ins[j]
+            if nop.startswith("v_") and _vgprs(nargs.split(",")[0].strip()) & data:
+                found.append((symbol, f"{op} {args}", f"{nop} {nargs}", waited))
+                continue
+            if nop == "s_endpgm":
+                continue
+            step = int(nargs) + 1 if nop == "s_nop" else 1
+            if nop == "s_branch" or nop.startswith("s_cbranch"):
+                imm = int(nargs.split()[0])
+                target = addr + 4 + 4 * (imm - 65536 if imm >= 32768 else imm)
+                if target in index:
+                    todo.append((index[target], waited + step))
+                if nop == "s_branch":
+                    continue
+            todo.append((j + 1, waited + step))
+    return found
+
+
 def main():
     args = [a for a in sys.argv[1:]]
     lib = DEFAULT_LIB

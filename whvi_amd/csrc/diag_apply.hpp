@@ -43,10 +43,14 @@ template <typename A> __device__ __forceinline__ A relu_(A v) { return (v > (A)0
 constexpr uint32_t DIAG_OPT_MEAN = 1u, DIAG_OPT_RELU_IN = 2u, DIAG_OPT_RELU_OUT = 4u, DIAG_OPT_PLAIN_ORDER = 8u, DIAG_OPT_PLAIN_STORES = 16u;
 
 // streaming store next to streaming loads: write-through + non-temporal (kernels.hpp: the written lines must not displace the
-// reads in L2), as a global store (per-lane addresses)
+// reads in L2), as a global store (per-lane addresses).  The s_nop is part of the store: a VALU write to the data VGPRs of a
+// store wider than 64 bits needs two wait states behind it on gfx950, and hipcc pads only the stores it emits itself, not
+// an asm statement.  Without it the compiler's next instruction (the g * x product of the batch sum) overwrote data[0]
+// before the store had read it, so grad_x took g * x instead of g * w in column 4c of every UNR-th row, now and then --
+// tests/test_build.py::test_no_store_data_hazard_in_the_shipped_library checks every wide store of the library for this
 __device__ __forceinline__ void st16_stream(u32x4 *p, const u32x4 &v)
 {
-    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(p), "v"(v) : "memory");
+    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt\n\ts_nop 1" ::"v"(p), "v"(v) : "memory");
 }
 
 template <typename T> struct Chunk { typedef typename Elem<T>::acc type __attribute__((ext_vector_type(Elem<T>::VEC))); };
@@ -557,6 +561,7 @@ inline int diag_apply_bwd_dispatch(void *grad_x, void *out, void *part, const vo
     const uint32_t mean_plus = (flags & WHVI_DIAG_MEAN_PLUS) ? 1u : 0u;
     // XCD-contiguous block order + write-through stores: measured (tools/diag_apply_rate.py, profiles/r04/diag_apply_rates.log)
     // +6.6 % on config 4's 9 GB (1.58 -> 1.48 ms, 6.06 TB/s) and -3 % on 2-3 GB streams (0.61 -> 0.63 ms): taken from 4 GiB up
+    // (the s_nop that st16_stream now carries costs nothing measurable: 1.47-1.48 ms with and without it, alternated runs)
     const bool long_stream = ((S * B) << log2d) * (int64_t)sizeof(T) * (grad_x ? 3 : 2) >= ((int64_t)4 << 30);
     const uint32_t opts = mean_plus | ((flags & WHVI_DIAG_RELU_IN) ? DIAG_OPT_RELU_IN : 0u) | ((flags & WHVI_DIAG_RELU_OUT) ? DIAG_OPT_RELU_OUT : 0u) |
                           (((flags & WHVI_DIAG_TUNE_PLAIN_ORDER) || !long_stream) ? (DIAG_OPT_PLAIN_ORDER | DIAG_OPT_PLAIN_STORES) : 0u);
