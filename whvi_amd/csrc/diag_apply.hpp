@@ -521,9 +521,14 @@ inline int diag_apply_dispatch(void *dst, const void *x, const void *s1, const v
                +9 %; NOT for one-row tiles of half the size (D = 2048: 34 -> 57 us).  WHVI_DIAG_TUNE_BIG_TILES: A/B */    \
             constexpr int NEED_ = (L > LV + 6) ? (1 << (L - LV - 6)) : 1;                                       \
             constexpr int KS_ = 4;                                                                              \
-            const bool small_ = !nt && NEED_ <= KS_ && KS_ < pick_k<T, L>() && !(flags & WHVI_DIAG_TUNE_BIG_TILES); \
-            if (small_) { if (shared) WHVI_DIAG_K(L, false, true, KS_); else WHVI_DIAG_K(L, false, false, KS_); } \
-            else if (shared) { if (nt) WHVI_DIAG(L, true, true); else WHVI_DIAG(L, false, true); }              \
+            /* (a compile-time guard: the quarter tiles of rows longer than one of them are never launched, so never built) */ \
+            if constexpr (NEED_ <= KS_ && KS_ < pick_k<T, L>()) {                                               \
+                if (!nt && !(flags & WHVI_DIAG_TUNE_BIG_TILES)) {                                               \
+                    if (shared) WHVI_DIAG_K(L, false, true, KS_); else WHVI_DIAG_K(L, false, false, KS_);       \
+                    break;                                                                                      \
+                }                                                                                               \
+            }                                                                                                   \
+            if (shared) { if (nt) WHVI_DIAG(L, true, true); else WHVI_DIAG(L, false, true); }                   \
             else { if (nt) WHVI_DIAG(L, true, false); else WHVI_DIAG(L, false, false); }                        \
         }                                                                                                       \
         break;
