@@ -390,6 +390,33 @@ int whvi_mlp_apply_bwd_f32(void *grad_w_in, void *grad_w_mid, void *grad_w_out, 
                            int32_t n_mid, const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
                            const void *w_out, int64_t S, int64_t B, int32_t log2d, int32_t relu, void *stream);
 
+/* The one-launch passes with a choice of activation: whvi_mlp_apply_f32 / whvi_mlp_apply_bwd_f32 with `int32_t act, int32_t
+ * act_bits` in place of `relu`.  act_bits has relu's layout (bit 0: behind the first layer, bit 1 + m: behind square layer m)
+ * and says which boundaries carry the activation `act`:
+ *   WHVI_MLP_ACT_RELU     relu(z), NaN passes -- exactly whvi_mlp_apply_f32 / whvi_mlp_apply_bwd_f32 with relu = act_bits
+ *   WHVI_MLP_ACT_SIGMOID  y = 1.0f / (1.0f + expf(-z))   (ATen's float sigmoid: ocml expf, IEEE division)
+ *                         backward d = (d * (1 - y)) * y  (torch's sigmoid_backward, on the recomputed y)
+ *   WHVI_MLP_ACT_TANH     y = tanhf(z)                    (ocml)
+ *                         backward d = d * (1 - y * y)    (torch's tanh_backward)
+ * Non-finite values follow torch: sigmoid(+inf) = 1, sigmoid(-inf) = 0, tanh(+-inf) = +-1, NaN passes.  A smooth activation
+ * sits where an nn.Sigmoid / nn.Tanh module sits on the three-launch route, before the next square layer's row poison (an
+ * activated +-inf is finite and poisons nothing).  The backward recomputes y from the forward's arithmetic; no mask, no state.
+ * Ranges, workspaces and every other rule are those of the ReLU entry points (whvi_mlp_apply_supported,
+ * whvi_mlp_apply_bwd_supported, whvi_mlp_apply_bwd_workspace); an unknown act, or act_bits beyond the n_mid + 1 boundaries,
+ * is WHVI_ERR_ARG.  Every argument check runs before any launch.  No allocation, no synchronisation: capture-safe. */
+#define WHVI_MLP_ACT_RELU    1
+#define WHVI_MLP_ACT_SIGMOID 2
+#define WHVI_MLP_ACT_TANH    3
+int whvi_mlp_apply_act_f32(void *y, const void *x, int32_t first, const void *w_in, const void *b_in, int32_t n_mid,
+                           const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
+                           const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t act,
+                           int32_t act_bits, void *stream);
+int whvi_mlp_apply_act_bwd_f32(void *grad_w_in, void *grad_w_mid, void *grad_w_out, void *grad_b, void *grad_x, void *work,
+                               int64_t work_floats, const void *g, const void *x, int32_t first, const void *w_in,
+                               const void *b_in, int32_t n_mid, const void *s1, const void *s2, const void *u,
+                               const void *b_mid, int32_t mid_bias, const void *w_out, int64_t S, int64_t B, int32_t log2d,
+                               int32_t act, int32_t act_bits, void *stream);
+
 /* whvi_reparam_kl_f32 with the eps draw inside the kernel: Philox4x32-10 + Box-Muller, one standard
  * normal per (matrix, sample, element), written to eps_out (J, S, D) for the backward pass / inspection.  The
  * generator state is three 64-bit words in DEVICE memory, state = {seed, launch offset, scratch (must be 0)}; the

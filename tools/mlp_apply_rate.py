@@ -24,14 +24,18 @@ SHAPES = {                      # name: (n_in, D, batch, samples)
     "toy": (1, 128, 500, 64),           # the toy notebook's 1 -> 128 -> 128 -> 1, eval_samples = 64
     "uci": (6, 128, 1000, 64),          # src/evaluation.py's WHVILinear(n_in, 128) network on a UCI-sized test set
     "config4": (3, 1024, 45730, 16),    # BASELINE config 4
+    "k8_1024": (8, 1024, 45730, 16),    # config 4's rows with 8 inputs: the K = 8, D = 1024 instantiation
 }
 
 
-def _net(n_in, D):
+ACTS = {"relu": nn.ReLU, "sigmoid": nn.Sigmoid, "tanh": nn.Tanh}    # --act: the activation at both boundaries
+
+
+def _net(n_in, D, act="relu"):
     from whvi_amd.layers import WHVILinear
     from whvi_amd.networks import WHVIRegression
     torch.manual_seed(0)
-    net = WHVIRegression([WHVILinear(n_in, D, bias=True), nn.ReLU(), WHVILinear(D, D, bias=True), nn.ReLU(),
+    net = WHVIRegression([WHVILinear(n_in, D, bias=True), ACTS[act](), WHVILinear(D, D, bias=True), ACTS[act](),
                           WHVILinear(D, 1, bias=True)])
     with torch.no_grad():
         for name, p in net.named_parameters():
@@ -54,14 +58,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--act", choices=sorted(ACTS), default="relu", help="the activation at both boundaries (sigmoid: the toy "
+                    "notebook's own WHVI model at the toy shape)")
     ap.add_argument("--shapes", default="toy,uci,config4")
     args = ap.parse_args()
     from whvi_amd import _hip
     from whvi_amd.graphs import GraphedPredictor
-    result = {"gpu": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats, "shapes": {}}
+    result = {"gpu": torch.cuda.get_device_name(0), "act": args.act, "iters": args.iters, "repeats": args.repeats, "shapes": {}}
     for name in args.shapes.split(","):
         n_in, D, B, S = SHAPES[name]
-        net = _net(n_in, D)
+        net = _net(n_in, D, args.act)
         x = torch.randn(B, n_in, device="cuda")
         outs = []
         for fused in (False, True):
@@ -70,7 +76,7 @@ def main():
             with torch.no_grad():
                 outs.append(net.forward_batched(x, S))
         kernel = _hip.last_kernel()
-        if not (kernel.startswith("whvi::mlp_apply_kernel<") and torch.equal(outs[0], outs[1])):
+        if not (kernel.startswith(("whvi::mlp_apply_kernel<", "whvi::mlp_smooth_apply_kernel<")) and torch.equal(outs[0], outs[1])):
             raise SystemExit(f"{name}: the fused pass ({kernel}) does not reproduce the three-launch route")
         del outs
         routes = {}

@@ -31,11 +31,14 @@ SHAPES = {                          # name: (n_in, D, batch, samples)
 }
 
 
-def _net(n_in, D):
+ACTS = {"relu": nn.ReLU, "sigmoid": nn.Sigmoid, "tanh": nn.Tanh}    # --act: the activation at both boundaries
+
+
+def _net(n_in, D, act="relu"):
     from whvi_amd.layers import WHVILinear
     from whvi_amd.networks import WHVIRegression
     torch.manual_seed(0)
-    net = WHVIRegression([WHVILinear(n_in, D, bias=True), nn.ReLU(), WHVILinear(D, D, bias=True), nn.ReLU(),
+    net = WHVIRegression([WHVILinear(n_in, D, bias=True), ACTS[act](), WHVILinear(D, D, bias=True), ACTS[act](),
                           WHVILinear(D, 1, bias=True)])
     with torch.no_grad():
         for name, p in net.named_parameters():
@@ -78,13 +81,15 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--act", choices=sorted(ACTS), default="relu", help="the activation at both boundaries (sigmoid: the toy "
+                    "notebook's own WHVI model at the toy shape)")
     ap.add_argument("--shapes", default=",".join(SHAPES))
     args = ap.parse_args()
     from whvi_amd import _hip
-    result = {"gpu": torch.cuda.get_device_name(0), "iters": args.iters, "repeats": args.repeats, "shapes": {}}
+    result = {"gpu": torch.cuda.get_device_name(0), "act": args.act, "iters": args.iters, "repeats": args.repeats, "shapes": {}}
     for name in args.shapes.split(","):
         n_in, D, B, S = SHAPES[name]
-        net = _net(n_in, D)
+        net = _net(n_in, D, args.act)
         net.train_samples = S
         x, y = torch.randn(B, n_in, device="cuda"), torch.randn(B, 1, device="cuda")
         ref, kernels = {}, []
@@ -102,7 +107,7 @@ def main():
             ref[fused] = (loss.detach(), [p.grad.clone() for p in net.parameters()])
         _hip.mlp_apply_bwd = bwd
         kernel = kernels[-1] if kernels else ""
-        ok = len(kernels) == 1 and kernel.startswith("whvi::mlp_apply_bwd_kernel<") and torch.equal(ref[False][0], ref[True][0])
+        ok = len(kernels) == 1 and kernel.startswith(("whvi::mlp_apply_bwd_kernel<", "whvi::mlp_smooth_apply_bwd_kernel<")) and torch.equal(ref[False][0], ref[True][0])
         for a, b in zip(ref[False][1], ref[True][1]):
             ok = ok and float((a - b).abs().max()) <= 1e-3 * float(b.abs().max())
         if not ok:

@@ -112,6 +112,11 @@ def _declare_f3(lib):
     lib.whvi_mlp_apply_bwd_f32.restype = ctypes.c_int
     lib.whvi_mlp_apply_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64, i64,
                                            i32, i32, vp]
+    lib.whvi_mlp_apply_act_f32.restype = ctypes.c_int
+    lib.whvi_mlp_apply_act_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp]
+    lib.whvi_mlp_apply_act_bwd_f32.restype = ctypes.c_int
+    lib.whvi_mlp_apply_act_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64,
+                                               i64, i32, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -622,6 +627,13 @@ def row_dot(x: torch.Tensor, w: torch.Tensor, bias: torch.Tensor = None, relu_in
 
 
 MLP_FIRST_COLUMN, MLP_FIRST_K4, MLP_FIRST_K8 = 1, 4, 8      # whvi_mlp_apply_f32's first-layer kinds (= K; 1 = column)
+MLP_ACTS = {"relu": 1, "sigmoid": 2, "tanh": 3}             # whvi_mlp_apply_act_f32's WHVI_MLP_ACT_*
+
+
+def _mlp_act(act: str) -> int:
+    if act not in MLP_ACTS:
+        raise RuntimeError(f"mlp_apply: unknown activation {act!r} (one of {', '.join(MLP_ACTS)})")
+    return MLP_ACTS[act]
 
 
 def mlp_apply_supported(first: int, n_mid: int, d: int) -> bool:
@@ -633,11 +645,14 @@ def mlp_apply_supported(first: int, n_mid: int, d: int) -> bool:
 
 
 def mlp_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor, u: torch.Tensor, b_mid,
-              w_out: torch.Tensor, b_out, *, mid_bias: int = 0, relu: int = 0) -> torch.Tensor:
+              w_out: torch.Tensor, b_out, *, mid_bias: int = 0, relu: int = 0, act: str = "relu") -> torch.Tensor:
     """One launch: the predictive pass of a WHVI regression network for all MC samples -- y (S, B); see
     whvi_mlp_apply_f32 in include/whvi_hip.h.  x (B, K) with w_in (S, D, K), K = 4 / 8, or x (B, 1) with w_in (S, D);
     s1, s2 (n_mid, D); u (n_mid, 1 + S, D); b_mid (n_mid, D) or None; w_out (S, D); b_in (D elements) / b_out (1) or None.
-    ``mid_bias`` bit m: square layer m has a bias; ``relu`` bit 0: ReLU behind the first layer, bit 1 + m: behind square layer m."""
+    ``mid_bias`` bit m: square layer m has a bias; ``relu``: the boundaries that carry the activation ``act`` -- bit 0 behind
+    the first layer, bit 1 + m behind square layer m.  ``act``: "relu" (whvi_mlp_apply_f32), "sigmoid" or "tanh"
+    (whvi_mlp_apply_act_f32)."""
+    code = _mlp_act(act)
     S, D = w_out.shape
     n_mid = s1.shape[0]
     first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
@@ -657,9 +672,14 @@ def mlp_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: t
     y = torch.empty((S, B), dtype=torch.float32, device=x.device)
     ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with _OnDevice(x.device):
-        rc = lib().whvi_mlp_apply_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid, s1.data_ptr(),
-                                      s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias), w_out.data_ptr(), ptr(b_out),
-                                      S, B, D.bit_length() - 1, int(relu), _stream(x))
+        if act == "relu":
+            rc = lib().whvi_mlp_apply_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid, s1.data_ptr(),
+                                          s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias), w_out.data_ptr(), ptr(b_out),
+                                          S, B, D.bit_length() - 1, int(relu), _stream(x))
+        else:
+            rc = lib().whvi_mlp_apply_act_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
+                                              s1.data_ptr(), s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias),
+                                              w_out.data_ptr(), ptr(b_out), S, B, D.bit_length() - 1, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply")
     return y
 
@@ -671,10 +691,13 @@ def mlp_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
 
 
 def mlp_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor,
-                  u: torch.Tensor, b_mid, w_out: torch.Tensor, *, mid_bias: int = 0, relu: int = 0, need_grad_x: bool = False):
-    """Backward of ``mlp_apply`` in one call (whvi_mlp_apply_bwd_f32): ``(grad_w_in, grad_w_mid (n_mid, S, D), grad_w_out
-    (S, D), grad_b ((1 + n_mid) D + 1: b_in, b_mid rows, b_out), grad_x (S, B, K) or None)`` from ``g`` = dL/dy (S, B) and
-    the forward's operands (same shapes as ``mlp_apply``)."""
+                  u: torch.Tensor, b_mid, w_out: torch.Tensor, *, mid_bias: int = 0, relu: int = 0, need_grad_x: bool = False,
+                  act: str = "relu"):
+    """Backward of ``mlp_apply`` in one call (whvi_mlp_apply_bwd_f32, or whvi_mlp_apply_act_bwd_f32 for ``act`` "sigmoid" /
+    "tanh"): ``(grad_w_in, grad_w_mid (n_mid, S, D), grad_w_out (S, D), grad_b ((1 + n_mid) D + 1: b_in, b_mid rows, b_out),
+    grad_x (S, B, K) or None)`` from ``g`` = dL/dy (S, B) and the forward's operands (same shapes and ``relu`` / ``act`` as
+    ``mlp_apply``)."""
+    code = _mlp_act(act)
     S, D = w_out.shape
     n_mid = s1.shape[0]
     first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
@@ -702,10 +725,13 @@ def mlp_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1
     with _OnDevice(dev):
         n = int(L.whvi_mlp_apply_bwd_workspace(S, B, first, n_mid, log2d))
         work = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
-        rc = L.whvi_mlp_apply_bwd_f32(grad_w_in.data_ptr(), grad_w_mid.data_ptr(), grad_w_out.data_ptr(), grad_b.data_ptr(),
-                                      ptr(grad_x), work.data_ptr(), n, g.data_ptr(), x.data_ptr(), first, w_in.data_ptr(),
-                                      ptr(b_in), n_mid, s1.data_ptr(), s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias),
-                                      w_out.data_ptr(), S, B, log2d, int(relu), _stream(x))
+        args = (grad_w_in.data_ptr(), grad_w_mid.data_ptr(), grad_w_out.data_ptr(), grad_b.data_ptr(), ptr(grad_x),
+                work.data_ptr(), n, g.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid, s1.data_ptr(),
+                s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias), w_out.data_ptr(), S, B, log2d)
+        if act == "relu":
+            rc = L.whvi_mlp_apply_bwd_f32(*args, int(relu), _stream(x))
+        else:
+            rc = L.whvi_mlp_apply_act_bwd_f32(*args, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply_bwd")
     return grad_w_in, grad_w_mid, grad_w_out, grad_b, grad_x
 

@@ -14,7 +14,11 @@
 //   transposed column layer           row_dot_kernel: the same chunk -> lane map (D >= 256: lane l holds chunks l, l + 64, ...;
 //                                     D < 256: D / 4 lanes per row), per-chunk x0 * w0 then fmaf, chunk partials in ascending
 //                                     order, the same __shfl_xor butterfly, + b_out
-// An nn.ReLU between two layers is relu_ (NaN passes) at that boundary wherever today's route applies it.
+// An nn.ReLU between two layers is relu_ (NaN passes) at that boundary wherever today's route applies it.  The smooth
+// activations (mlp_smooth_apply_kernel, ACT = WHVI_MLP_ACT_SIGMOID / _TANH) run ATen's float formulas at the same places:
+//   sigmoid  1.0f / (1.0f + expf(-z))    (ocml expf, IEEE division: sigmoid(+inf) = 1, sigmoid(-inf) = 0, NaN passes)
+//   tanh     tanhf(z)                     (ocml; tanh(+-inf) = +-1, NaN passes)
+// and, as on today's route, before the next square layer's row poison.
 //
 // Geometry: a block owns (sample s, a slab of batch rows).  It first stages that sample's operands in LDS -- W1 transposed to
 // [c][n], b_in, per square layer its diagonal and bias, w_out: 4 D (K + 2 + 2 n_mid) bytes, at most 64 KiB -- then each wave
@@ -46,6 +50,29 @@ template <int LOG2D> struct MlpGeom {
     static constexpr int R = C >= 4 ? 16 / C : 8;         // rows per lane group and iteration (R * C * 4 <= 64 hidden floats)
     static constexpr int RPI = G * R;                     // rows per wave iteration
 };
+
+// Activation policies of the fused passes.  fwd: the activation at a boundary; bwd(d, y): its gradient from the incoming
+// gradient d and the activation's output y, torch's formula (sigmoid_backward / tanh_backward) in the same order.  The ReLU
+// policy's backward is not a formula of y: its kernels recompute masks (mlp_square_layer<MASK>, mlp_bwd_rows).
+struct MlpRelu {
+    static constexpr bool SMOOTH = false;
+    __device__ static __forceinline__ float fwd(float z) { return relu_(z); }
+};
+struct MlpSigmoid {
+    static constexpr bool SMOOTH = true;
+    __device__ static __forceinline__ float fwd(float z) { return 1.0f / (1.0f + expf(-z)); }          // ATen's sigmoid (float)
+    __device__ static __forceinline__ float bwd(float d, float y) { return (d * (1.0f - y)) * y; }
+};
+struct MlpTanh {
+    static constexpr bool SMOOTH = true;
+    __device__ static __forceinline__ float fwd(float z) { return tanhf(z); }
+    __device__ static __forceinline__ float bwd(float d, float y) { return d * (1.0f - y * y); }
+};
+// WHVI_MLP_ACT_* -> policy (the smooth kernels carry the ABI's number as their last template argument)
+template <int ACT> struct MlpAct;
+template <> struct MlpAct<WHVI_MLP_ACT_RELU> { using type = MlpRelu; };
+template <> struct MlpAct<WHVI_MLP_ACT_SIGMOID> { using type = MlpSigmoid; };
+template <> struct MlpAct<WHVI_MLP_ACT_TANH> { using type = MlpTanh; };
 
 // diag_apply_kernel's row-poison rule for the R rows a lane group holds (rare path, behind a wave ballot)
 template <int L, int R, int C>
@@ -126,10 +153,11 @@ __device__ __forceinline__ void mlp_load_x(float (&xv)[R][KIN], const float *__r
     }
 }
 
-// first layer: small_k_apply_kernel's +0-initialised fmaf chain (KIN = 4 / 8) or the column layer's plain product, + b_in, relu_
-template <int LOG2D, int KIN, int R>
+// first layer: small_k_apply_kernel's +0-initialised fmaf chain (KIN = 4 / 8) or the column layer's plain product, + b_in,
+// the activation (act0)
+template <int LOG2D, int KIN, int R, typename ACT = MlpRelu>
 __device__ __forceinline__ void mlp_first_layer(float (&h)[R][MlpGeom<LOG2D>::C][4], const float (&xv)[R][KIN], const float *lw1,
-                                                const float *lbi, uint32_t col, bool has_b_in, bool relu0)
+                                                const float *lbi, uint32_t col, bool has_b_in, bool act0)
 {
     using Gm = MlpGeom<LOG2D>;
     constexpr int D = Gm::D, L = Gm::L, C = Gm::C;
@@ -154,19 +182,20 @@ __device__ __forceinline__ void mlp_first_layer(float (&h)[R][MlpGeom<LOG2D>::C]
                     for (int c = 0; c < KIN; ++c) a = __builtin_fmaf(xv[r][c], wc[c][e], a);
                 }
                 if (has_b_in) a = a + bc[e];
-                if (relu0) a = relu_(a);
+                if (act0) a = ACT::fwd(a);
                 h[r][j][e] = a;
             }
     }
 }
 
-// one square layer in place: diag_apply_kernel's row poison, r * wbar_diag + 0, + bias, relu_.  lw: the layer's diagonal,
-// lb: its bias (LDS).  MASK (the backward): bit (r C + j) 4 + e of *mask = the fused ReLU's gradient passes there, as
-// whvi_diag_apply_bwd recomputes it -- from the layer's input BEFORE the poison: !(relu_(h * w (+ b)) <= 0), NaN passes
-template <int LOG2D, int R, bool MASK = false>
+// one square layer in place: diag_apply_kernel's row poison, r * wbar_diag + 0, + bias, the activation (hr).  lw: the layer's
+// diagonal, lb: its bias (LDS).  MASK (the ReLU backward): bit (r C + j) 4 + e of *mask = the fused ReLU's gradient passes
+// there, as whvi_diag_apply_bwd recomputes it -- from the layer's input BEFORE the poison: !(relu_(h * w (+ b)) <= 0), NaN passes
+template <int LOG2D, int R, bool MASK = false, typename ACT = MlpRelu>
 __device__ __forceinline__ void mlp_square_layer(float (&h)[R][MlpGeom<LOG2D>::C][4], const float *lw, const float *lb,
                                                  uint32_t col, bool hb, bool hr, uint32_t *mask = nullptr)
 {
+    static_assert(!MASK || !ACT::SMOOTH, "masks are the ReLU backward's");
     using Gm = MlpGeom<LOG2D>;
     constexpr int L = Gm::L, C = Gm::C;
     typedef float f4 __attribute__((ext_vector_type(4)));
@@ -213,7 +242,7 @@ __device__ __forceinline__ void mlp_square_layer(float (&h)[R][MlpGeom<LOG2D>::C
                 if constexpr (MASK) {
                     if (!(relu_(v) <= 0.0f)) mk |= 1u << ((r * C + j) * 4 + e);
                 }
-                if (hr) v = relu_(v);
+                if (hr) v = ACT::fwd(v);
                 h[r][j][e] = v;
             }
     }
@@ -224,7 +253,82 @@ __device__ __forceinline__ void mlp_square_layer(float (&h)[R][MlpGeom<LOG2D>::C
 
 // y[s, b] for b in the block's slab.  x : (B, KIN); w_in : (S, D, KIN) (KIN = 4 / 8) or (S, D) (KIN = 1); s1, s2, b_mid :
 // (n_mid, D); u : (n_mid, 1 + S, D) (mean row first, whvi_diag_apply's WHVI_DIAG_MEAN_PLUS layout); w_out : (S, D).
-// relu bit 0: behind the first layer, bit 1 + m: behind square layer m.  mid_bias bit m: square layer m has a bias.
+// act bit 0: ACT behind the first layer, bit 1 + m: behind square layer m.  mid_bias bit m: square layer m has a bias.
+// TWIN: mlp_apply_kernel below repeats this body statement for statement with ACT = MlpRelu (see there why); a change to
+// one -- tails, geometry, the row dot -- must be made in both.
+template <int LOG2D, int KIN, typename ACT>
+__device__ __forceinline__ void
+mlp_apply_block(float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ w_in,
+                const float *__restrict__ b_in, const float *__restrict__ s1, const float *__restrict__ s2,
+                const float *__restrict__ u, const float *__restrict__ b_mid, const float *__restrict__ w_out,
+                const float *__restrict__ b_out, uint32_t S, uint32_t B, uint32_t n_mid, uint32_t mid_bias, uint32_t act,
+                uint32_t slab_rows, uint32_t n_slabs)
+{
+    using Gm = MlpGeom<LOG2D>;
+    constexpr int D = Gm::D, L = Gm::L, C = Gm::C, R = Gm::R, RPI = Gm::RPI;
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    extern __shared__ __attribute__((aligned(16))) float mlp_lds[];
+    float *lw1 = mlp_lds;                    // [c][n]: KIN rows of D
+    float *lbi = lw1 + KIN * D;              // b_in
+    float *lmid = lbi + D;                   // square layer m: diagonal at 2 m D, bias at (2 m + 1) D
+    float *lwo = lmid + 2 * n_mid * D;       // w_out
+
+    const uint32_t s = blockIdx.x / n_slabs, slab = blockIdx.x - s * n_slabs;
+    const uint32_t b0 = slab * slab_rows, b1 = b0 + slab_rows < B ? b0 + slab_rows : B;
+
+    mlp_stage_operands<LOG2D, KIN>(mlp_lds, s, w_in, b_in, s1, s2, u, b_mid, w_out, S, n_mid, mid_bias);
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t grp = (uint32_t)lane / L, col = (uint32_t)lane % L;      // the lane's row group and first chunk
+    const bool has_b_in = b_in != nullptr;
+    const float bo = b_out != nullptr ? b_out[0] : 0.0f;
+    float *ys = y + (size_t)s * B;
+    for (uint32_t rb = b0 + wave * RPI; rb < b1; rb += 4 * RPI) {
+        // D >= 512 with a smooth activation: re-read the operands from LDS on every iteration instead of letting them be
+        // hoisted into registers (as mlp_apply_bwd_block does): tanhf's temporaries on top took K = 8, D = 1024 past 256
+        if constexpr (C >= 4) asm volatile("" ::: "memory");
+        const uint32_t r0 = rb + grp * R;                 // rows r0 .. r0 + R - 1 (past b1: a valid row's operands, never stored)
+        float h[R][C][4];
+        {   // ---- first layer
+            float xv[R][KIN];
+            mlp_load_x<KIN, R>(xv, x, r0, b1);
+            mlp_first_layer<LOG2D, KIN, R, ACT>(h, xv, lw1, lbi, col, has_b_in, (act & 1u) != 0);
+        }
+        // ---- square layers
+        for (uint32_t m = 0; m < n_mid; ++m)
+            mlp_square_layer<LOG2D, R, false, ACT>(h, lmid + 2 * m * D, lmid + (2 * m + 1) * D, col, (mid_bias >> m) & 1u,
+                                                   (act >> (m + 1)) & 1u);
+        // ---- transposed column layer: row_dot_kernel's partials, order and butterfly
+        float acc[R];
+#pragma unroll
+        for (int j = 0; j < C; ++j) {
+            const f4 wc = reinterpret_cast<const f4 *>(lwo)[col + j * L];
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                float a = h[r][j][0] * wc[0];
+#pragma unroll
+                for (int e = 1; e < 4; ++e) a = __builtin_fmaf(h[r][j][e], wc[e], a);
+                acc[r] = j == 0 ? a : acc[r] + a;
+            }
+        }
+        float outv = 0.0f;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            float v = acc[r];
+#pragma unroll
+            for (int m = 1; m < L; m <<= 1) v = v + __shfl_xor(v, m, 64);
+            if (col == (uint32_t)r) outv = v;              // every lane of the group holds the sum: lane r keeps row r's
+        }
+        if (b_out != nullptr) outv = outv + bo;
+        if (col < (uint32_t)R && r0 + col < b1) ys[r0 + col] = outv;      // R neighbouring floats per lane group
+    }
+}
+
+// The ReLU pass.  It keeps a body of its own rather than calling mlp_apply_block, whose code is the same statement for statement:
+// behind a call the inliner optimises the body before the kernel, and the ReLU kernels' code would change.  TWIN of
+// mlp_apply_block: a change to one must be made in both (tests/test_mlp_smooth_gpu.py checks both against float64).
 template <typename T, int LOG2D, int KIN>      // (T = float; named so that whvi_last_kernel prints the real symbol)
 __global__ void __launch_bounds__(256)
 mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ w_in, const float *__restrict__ b_in,
@@ -290,12 +394,35 @@ mlp_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float
     }
 }
 
-inline int mlp_apply_dispatch(void *y, const void *x, int32_t first, const void *w_in, const void *b_in, int32_t n_mid,
-                              const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
-                              const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t relu,
-                              void *stream)
+// the same pass with a smooth activation, ACT = WHVI_MLP_ACT_SIGMOID / _TANH, at the boundaries of `act`
+template <typename T, int LOG2D, int KIN, int ACT>
+__global__ void __launch_bounds__(256)
+mlp_smooth_apply_kernel(float *__restrict__ y, const float *__restrict__ x, const float *__restrict__ w_in,
+                        const float *__restrict__ b_in, const float *__restrict__ s1, const float *__restrict__ s2,
+                        const float *__restrict__ u, const float *__restrict__ b_mid, const float *__restrict__ w_out,
+                        const float *__restrict__ b_out, uint32_t S, uint32_t B, uint32_t n_mid, uint32_t mid_bias, uint32_t act,
+                        uint32_t slab_rows, uint32_t n_slabs)
 {
-    g_err[0] = 0;
+    static_assert(MlpAct<ACT>::type::SMOOTH, "the ReLU pass is mlp_apply_kernel");
+    mlp_apply_block<LOG2D, KIN, typename MlpAct<ACT>::type>(y, x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, S, B, n_mid,
+                                                             mid_bias, act, slab_rows, n_slabs);
+}
+
+// The launch of one call, from mlp_apply_check
+struct MlpLaunch {
+    dim3 grid;
+    size_t lds;
+    uint32_t slab_rows, n_slabs;
+};
+
+// Every argument check of whvi_mlp_apply_f32 / whvi_mlp_apply_act_f32, before any launch; `bits` (named `bits_name` in the
+// message) are the activation bits.  WHVI_OK with ln.grid.x = 0: nothing to launch.
+inline int mlp_apply_check(MlpLaunch &ln, const void *y, const void *x, int32_t first, const void *w_in, const void *b_in,
+                           int32_t n_mid, const void *s1, const void *s2, const void *u, const void *b_mid, int32_t mid_bias,
+                           const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t bits,
+                           const char *bits_name)
+{
+    ln.grid = dim3(0);
     if (S < 0 || B < 0) return fail(WHVI_ERR_ARG, "whvi_mlp_apply: negative size%s", "");
     if (first != WHVI_MLP_FIRST_COLUMN && first != WHVI_MLP_FIRST_K4 && first != WHVI_MLP_FIRST_K8)
         return fail(WHVI_ERR_ARG, "whvi_mlp_apply: unknown first-layer kind%s %lld", "", first);
@@ -305,7 +432,7 @@ inline int mlp_apply_dispatch(void *y, const void *x, int32_t first, const void 
     if (!mlp_supported(first, n_mid, log2d))
         return fail(WHVI_ERR_SIZE, "whvi_mlp_apply: the operands of one sample%s need %lld B of LDS (64 KiB at most)", "",
                     mlp_lds_bytes(first, n_mid, log2d));
-    if (relu & ~((1 << (n_mid + 1)) - 1)) return fail(WHVI_ERR_ARG, "whvi_mlp_apply: unknown relu bits%s 0x%llx", "", relu);
+    if (bits & ~((1 << (n_mid + 1)) - 1)) return fail(WHVI_ERR_ARG, "whvi_mlp_apply: unknown %s bits 0x%llx", bits_name, bits);
     if (mid_bias & ~((1 << n_mid) - 1)) return fail(WHVI_ERR_ARG, "whvi_mlp_apply: unknown mid_bias bits%s 0x%llx", "", mid_bias);
     const int64_t rows = S * B;
     if (rows == 0) return WHVI_OK;
@@ -335,31 +462,11 @@ inline int mlp_apply_dispatch(void *y, const void *x, int32_t first, const void 
     const int64_t slab_rows = (B + n_slabs - 1) / n_slabs;
     n_slabs = (B + slab_rows - 1) / slab_rows;
     if (n_slabs * S >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_mlp_apply: too many blocks%s", "");
-    const size_t lds = (size_t)mlp_lds_bytes(first, n_mid, log2d);
-    const dim3 grid((unsigned)(n_slabs * S));
-    hipStream_t st = (hipStream_t)stream;
-#define WHVI_MLP(L, K)                                                                                          \
-    do {                                                                                                        \
-        if constexpr (mlp_lds_bytes(K, 1, L) <= MLP_MAX_LDS) {                                                  \
-            note_launch<float>("mlp_apply_kernel", L, K);                                                       \
-            hipLaunchKernelGGL((mlp_apply_kernel<float, L, K>), grid, dim3(256), lds, st, (float *)y, (const float *)x, \
-                               (const float *)w_in, (const float *)b_in, (const float *)s1, (const float *)s2,   \
-                               (const float *)u, (const float *)b_mid, (const float *)w_out, (const float *)b_out, \
-                               (uint32_t)S, (uint32_t)B, (uint32_t)n_mid, (uint32_t)mid_bias, (uint32_t)relu,    \
-                               (uint32_t)slab_rows, (uint32_t)n_slabs);                                         \
-        }                                                                                                       \
-    } while (0)
-#define WHVI_CASE(L)                                                                                            \
-    case L:                                                                                                     \
-        if (first == 1) WHVI_MLP(L, 1); else if (first == 4) WHVI_MLP(L, 4); else WHVI_MLP(L, 8);               \
-        break;
-    switch (log2d) {
-        WHVI_CASE(6) WHVI_CASE(7) WHVI_CASE(8) WHVI_CASE(9) WHVI_CASE(10) WHVI_CASE(11)
-    default: break;
-    }
-#undef WHVI_CASE
-#undef WHVI_MLP
-    return after_launch("mlp_apply");
+    ln.lds = (size_t)mlp_lds_bytes(first, n_mid, log2d);
+    ln.grid = dim3((unsigned)(n_slabs * S));
+    ln.slab_rows = (uint32_t)slab_rows;
+    ln.n_slabs = (uint32_t)n_slabs;
+    return WHVI_OK;
 }
 
 }  // namespace whvi

@@ -12,6 +12,8 @@
 //   first layer                         ReLU behind it: column layer (the square layer's relu_in) d = 0 where h_0 <= 0; stacked
 //                                      layer (SmallKApplyFunction) d = d * (h_0 > 0);  grad_b_in += d;
 //                                      grad_w_in[n, c] += d * x[c];  grad_x[s, b, c] = sum_n d * w_in[n, c] (a butterfly)
+// With a smooth activation (mlp_smooth_apply_bwd_kernel, ACT = WHVI_MLP_ACT_SIGMOID / _TANH) the two activation steps above are
+// torch's formula on the recomputed output y (hs[]): sigmoid d = (d * (1 - y)) * y, tanh d = d * (1 - y * y) -- no masks.
 // Each lane keeps the sums of its hidden units over its rows in registers (C * 4 * (K + 2 + 2 n_mid) floats); lane groups of a
 // wave combine by a butterfly, the four waves through LDS in wave order, and the block writes one partial per field to its slab
 // of the workspace.  A second, tiny launch inside the same call adds the slabs in ascending order (samples in ascending order
@@ -39,7 +41,8 @@ inline bool mlp_bwd_supported(int kin, int n_mid, int log2d)
     return mlp_supported(kin, n_mid, log2d) && n_mid <= MLP_BWD_MAX_MID && log2d <= MLP_BWD_MAX_LOG2D;
 }
 
-template <int LOG2D, int KIN, int NMID, bool TAIL>
+// relu: the act bits (ACT at those boundaries)
+template <int LOG2D, int KIN, int NMID, bool TAIL, typename ACT = MlpRelu>
 __device__ __forceinline__ void mlp_bwd_rows(
     uint32_t r0, uint32_t b1, const float *__restrict__ x, const float *__restrict__ gs, float *__restrict__ gxs,
     const float *lw1, const float *lbi, const float *lmid, const float *lwo, uint32_t col, bool has_b_in, uint32_t mid_bias,
@@ -54,7 +57,7 @@ __device__ __forceinline__ void mlp_bwd_rows(
     float xv[R][KIN];
     mlp_load_x<KIN, R>(xv, x, r0, b1);
     float hs[NMID + 1][R][C][4];
-    mlp_first_layer<LOG2D, KIN, R>(hs[0], xv, lw1, lbi, col, has_b_in, (relu & 1u) != 0);
+    mlp_first_layer<LOG2D, KIN, R, ACT>(hs[0], xv, lw1, lbi, col, has_b_in, (relu & 1u) != 0);
     uint32_t mask[NMID];
 #pragma unroll
     for (int m = 0; m < NMID; ++m) {
@@ -64,8 +67,8 @@ __device__ __forceinline__ void mlp_bwd_rows(
             for (int j = 0; j < C; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) hs[m + 1][r][j][e] = hs[m][r][j][e];
-        mlp_square_layer<LOG2D, R, true>(hs[m + 1], lmid + 2 * m * D, lmid + (2 * m + 1) * D, col, (mid_bias >> m) & 1u,
-                                         (relu >> (m + 1)) & 1u, &mask[m]);
+        mlp_square_layer<LOG2D, R, !ACT::SMOOTH, ACT>(hs[m + 1], lmid + 2 * m * D, lmid + (2 * m + 1) * D, col, (mid_bias >> m) & 1u,
+                                                      (relu >> (m + 1)) & 1u, &mask[m]);
     }
     float gv[R];
 #pragma unroll
@@ -90,13 +93,19 @@ __device__ __forceinline__ void mlp_bwd_rows(
                 gwo[j][e] = __builtin_fmaf(hs[NMID][r][j][e], gv[r], gwo[j][e]);
 #pragma unroll
                 for (int m = NMID - 1; m >= 0; --m) {
-                    if (((relu >> (m + 1)) & 1u) && !((mask[m] >> ((r * C + j) * 4 + e)) & 1u)) d = 0.0f;
+                    if constexpr (ACT::SMOOTH) {
+                        if ((relu >> (m + 1)) & 1u) d = ACT::bwd(d, hs[m + 1][r][j][e]);
+                    } else {
+                        if (((relu >> (m + 1)) & 1u) && !((mask[m] >> ((r * C + j) * 4 + e)) & 1u)) d = 0.0f;
+                    }
                     gwm[m][j][e] = __builtin_fmaf(d, hs[m][r][j][e], gwm[m][j][e]);
                     gbm[m][j][e] = gbm[m][j][e] + d;
                     d = d * lmid[2 * m * D + 4 * q + e];
                 }
                 if (relu & 1u) {
-                    if constexpr (KIN == 1) {
+                    if constexpr (ACT::SMOOTH) {
+                        d = ACT::bwd(d, hs[0][r][j][e]);
+                    } else if constexpr (KIN == 1) {
                         if (hs[0][r][j][e] <= 0.0f) d = 0.0f;     // the square layer's relu_in: NaN passes
                     } else {
                         d = d * (hs[0][r][j][e] > 0.0f ? 1.0f : 0.0f);   // SmallKApplyFunction: g * (out > 0)
@@ -127,7 +136,101 @@ __device__ __forceinline__ void mlp_bwd_rows(
     }
 }
 
-// g : (S, B); gx : (S, B, KIN) or NULL; part : (S * n_slabs) blocks of mlp_bwd_part_floats floats.  Operands as mlp_apply_kernel.
+// g : (S, B); gx : (S, B, KIN) or NULL; part : (S * n_slabs) blocks of mlp_bwd_part_floats floats.  Operands as mlp_apply_kernel;
+// relu: the act bits (ACT at those boundaries).  TWIN: mlp_apply_bwd_kernel below repeats this body statement for statement
+// with ACT = MlpRelu (see mlp_apply_kernel for why); a change to one -- tails, the LDS reduction, the slab layout -- must be
+// made in both.
+template <int LOG2D, int KIN, int NMID, typename ACT>
+__device__ __forceinline__ void
+mlp_apply_bwd_block(float *__restrict__ part, float *__restrict__ gx, const float *__restrict__ g,
+                    const float *__restrict__ x, const float *__restrict__ w_in, const float *__restrict__ b_in,
+                    const float *__restrict__ s1, const float *__restrict__ s2, const float *__restrict__ u,
+                    const float *__restrict__ b_mid, const float *__restrict__ w_out, uint32_t S, uint32_t B, uint32_t mid_bias,
+                    uint32_t relu, uint32_t slab_rows, uint32_t n_slabs)
+{
+    using Gm = MlpGeom<LOG2D>;
+    constexpr int D = Gm::D, L = Gm::L, G = Gm::G, C = Gm::C, RPI = MlpBwdGeom<LOG2D>::RPI;
+    constexpr int F = (int)mlp_bwd_fields(KIN, NMID);
+    extern __shared__ __attribute__((aligned(16))) float mlp_lds[];
+    float *lw1 = mlp_lds, *lbi = lw1 + KIN * D, *lmid = lbi + D, *lwo = lmid + 2 * NMID * D;
+
+    const uint32_t s = blockIdx.x / n_slabs, slab = blockIdx.x - s * n_slabs;
+    const uint32_t b0 = slab * slab_rows, b1 = b0 + slab_rows < B ? b0 + slab_rows : B;
+    mlp_stage_operands<LOG2D, KIN>(mlp_lds, s, w_in, b_in, s1, s2, u, b_mid, w_out, S, NMID, mid_bias);
+    __syncthreads();
+
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t grp = (uint32_t)lane / L, col = (uint32_t)lane % L;
+    const bool has_b_in = b_in != nullptr;
+    float gwi[C][4][KIN], gbi[C][4], gwm[NMID][C][4], gbm[NMID][C][4], gwo[C][4], gsum = 0.0f;
+#pragma unroll
+    for (int j = 0; j < C; ++j)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+#pragma unroll
+            for (int c = 0; c < KIN; ++c) gwi[j][e][c] = 0.0f;
+            gbi[j][e] = gwo[j][e] = 0.0f;
+#pragma unroll
+            for (int m = 0; m < NMID; ++m) gwm[m][j][e] = gbm[m][j][e] = 0.0f;
+        }
+    const float *gs = g + (size_t)s * B;
+    float *gxs = gx != nullptr ? gx + (size_t)s * B * KIN : nullptr;
+    for (uint32_t rb = b0 + wave * RPI; rb < b1; rb += 4 * RPI) {
+        // D = 1024: re-read the operands from LDS on every iteration instead of letting them be hoisted into registers (as many
+        // as the accumulators: 366 instead of 2xx VGPRs at K = 4, and a spill at K = 8 with two square layers)
+        if constexpr (C >= 4) asm volatile("" ::: "memory");
+        const uint32_t r0 = rb + grp * MlpBwdGeom<LOG2D>::R;
+        if (rb + RPI <= b1)
+            mlp_bwd_rows<LOG2D, KIN, NMID, false, ACT>(r0, b1, x, gs, gxs, lw1, lbi, lmid, lwo, col, has_b_in, mid_bias, relu, gwi,
+                                                       gbi, gwm, gbm, gwo, gsum);
+        else
+            mlp_bwd_rows<LOG2D, KIN, NMID, true, ACT>(r0, b1, x, gs, gxs, lw1, lbi, lmid, lwo, col, has_b_in, mid_bias, relu, gwi,
+                                                      gbi, gwm, gbm, gwo, gsum);
+    }
+
+    // ---- the block's sums: lane groups of a wave by a butterfly, then the waves through LDS in wave order
+    auto each = [&](auto &&fn) {
+#pragma unroll
+        for (int j = 0; j < C; ++j)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const uint32_t n = 4 * (col + j * L) + e;
+#pragma unroll
+                for (int c = 0; c < KIN; ++c) fn(gwi[j][e][c], c * D + n);
+                fn(gbi[j][e], KIN * D + n);
+#pragma unroll
+                for (int m = 0; m < NMID; ++m) {
+                    fn(gwm[m][j][e], (KIN + 1 + m) * D + n);
+                    fn(gbm[m][j][e], (KIN + 1 + NMID + m) * D + n);
+                }
+                fn(gwo[j][e], (KIN + 1 + 2 * NMID) * D + n);
+            }
+        fn(gsum, F * D);
+    };
+    if constexpr (G > 1) {
+        each([&](float &v, uint32_t) {
+#pragma unroll
+            for (int m = L; m < 64; m <<= 1) v = v + __shfl_xor(v, m, 64);
+        });
+    }
+    __syncthreads();                                       // every wave is done with the operands: the LDS holds the sums now
+    float *red = mlp_lds;
+    for (int w = 0; w < 4; ++w) {
+        if (wave == w && grp == 0) {
+            each([&](float &v, uint32_t i) {
+                if (i == (uint32_t)(F * D) && col != 0) return;
+                red[i] = w == 0 ? v : red[i] + v;
+            });
+        }
+        __syncthreads();
+    }
+    float *p = part + (size_t)blockIdx.x * mlp_bwd_part_floats(KIN, NMID, LOG2D);
+    for (uint32_t i = threadIdx.x; i <= (uint32_t)(F * D); i += 256) p[i] = red[i];
+}
+
+// The ReLU backward, with a body of its own for the reason mlp_apply_kernel has one (mlp_apply.hpp).  TWIN of
+// mlp_apply_bwd_block: a change to one must be made in both.
 template <typename T, int LOG2D, int KIN, int NMID>
 __global__ void __launch_bounds__(256)
 mlp_apply_bwd_kernel(float *__restrict__ part, float *__restrict__ gx, const float *__restrict__ g, const float *__restrict__ x,
@@ -217,41 +320,24 @@ mlp_apply_bwd_kernel(float *__restrict__ part, float *__restrict__ gx, const flo
     for (uint32_t i = threadIdx.x; i <= (uint32_t)(F * D); i += 256) p[i] = red[i];
 }
 
-// Slabs in ascending order.  Thread t < S (K + n_mid + 1) D: one per-sample output, (field, s, n) with n fastest; then
-// (1 + n_mid) D + 1 bias sums over samples and slabs.
+// the backward of mlp_smooth_apply_kernel: ACT = WHVI_MLP_ACT_SIGMOID / _TANH at the boundaries of `act`
+template <typename T, int LOG2D, int KIN, int NMID, int ACT>
 __global__ void __launch_bounds__(256)
-mlp_apply_bwd_finish_kernel(float *__restrict__ gw_in, float *__restrict__ gw_mid, float *__restrict__ gw_out,
-                            float *__restrict__ gb, const float *__restrict__ part, uint32_t S, uint32_t n_slabs, uint32_t kin,
-                            uint32_t n_mid, uint32_t log2d)
+mlp_smooth_apply_bwd_kernel(float *__restrict__ part, float *__restrict__ gx, const float *__restrict__ g,
+                            const float *__restrict__ x, const float *__restrict__ w_in, const float *__restrict__ b_in,
+                            const float *__restrict__ s1, const float *__restrict__ s2, const float *__restrict__ u,
+                            const float *__restrict__ b_mid, const float *__restrict__ w_out, uint32_t S, uint32_t B,
+                            uint32_t mid_bias, uint32_t act, uint32_t slab_rows, uint32_t n_slabs)
 {
-    const uint32_t D = 1u << log2d, F = kin + 2 + 2 * n_mid;
-    const size_t ps = ((size_t)F << log2d) + 4;
-    const uint32_t n_per = S * (kin + n_mid + 1) * D, n_bias = (1 + n_mid) * D + 1;
-    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_per + n_bias) return;
-    if (t < n_per) {
-        const uint32_t n = t & (D - 1), fs = t >> log2d, s = fs % S, fi = fs / S;
-        const uint32_t field = fi < kin ? fi : (fi < kin + n_mid ? fi + 1 : F - 1);
-        const float *p = part + (size_t)s * n_slabs * ps + (size_t)field * D + n;
-        float a = 0.0f;
-        for (uint32_t k = 0; k < n_slabs; ++k) a = a + p[(size_t)k * ps];
-        if (fi < kin) gw_in[((size_t)s * D + n) * kin + fi] = a;
-        else if (fi < kin + n_mid) gw_mid[((size_t)(fi - kin) * S + s) * D + n] = a;
-        else gw_out[(size_t)s * D + n] = a;
-        return;
-    }
-    const uint32_t tb = t - n_per;
-    size_t off;
-    if (tb < (1 + n_mid) * D) {
-        const uint32_t fb = tb >> log2d, n = tb & (D - 1);
-        off = (size_t)(fb == 0 ? kin : kin + 1 + n_mid + (fb - 1)) * D + n;
-    } else {
-        off = (size_t)F * D;
-    }
-    float a = 0.0f;
-    for (size_t k = 0; k < (size_t)S * n_slabs; ++k) a = a + part[k * ps + off];
-    gb[tb] = a;
+    static_assert(MlpAct<ACT>::type::SMOOTH, "the ReLU backward is mlp_apply_bwd_kernel");
+    mlp_apply_bwd_block<LOG2D, KIN, NMID, typename MlpAct<ACT>::type>(part, gx, g, x, w_in, b_in, s1, s2, u, b_mid, w_out,
+                                                                       S, B, mid_bias, act, slab_rows, n_slabs);
 }
+
+// The finishing launch (mlp_apply_bwd_finish_kernel, defined once in mlp_apply_bwd.hip): the slabs' partial sums in `work` into
+// the gradients, in ascending slab and sample order
+int mlp_apply_bwd_finish(void *grad_w_in, void *grad_w_mid, void *grad_w_out, void *grad_b, const void *work, int64_t S,
+                         int64_t n_slabs, int32_t first, int32_t n_mid, int32_t log2d, hipStream_t st);
 
 // slabs per sample: about two blocks per CU over all samples, at least 256 rows (4 waves x 4 iterations of the widest group)
 inline int64_t mlp_bwd_slabs(int64_t S, int64_t B)
@@ -265,20 +351,30 @@ inline int64_t mlp_bwd_slabs(int64_t S, int64_t B)
     return (B + slab_rows - 1) / slab_rows;
 }
 
-inline int mlp_apply_bwd_dispatch(void *grad_w_in, void *grad_w_mid, void *grad_w_out, void *grad_b, void *grad_x, void *work,
-                                  int64_t work_floats, const void *g, const void *x, int32_t first, const void *w_in,
-                                  const void *b_in, int32_t n_mid, const void *s1, const void *s2, const void *u,
-                                  const void *b_mid, int32_t mid_bias, const void *w_out, int64_t S, int64_t B, int32_t log2d,
-                                  int32_t relu, void *stream)
+// The launch of one call, from mlp_apply_bwd_check
+struct MlpBwdLaunch {
+    dim3 grid;
+    size_t lds;
+    uint32_t slab_rows, n_slabs;
+};
+
+// Every argument check of whvi_mlp_apply_bwd_f32 / whvi_mlp_apply_act_bwd_f32, before any launch; `bits` (named `bits_name` in
+// the message) are the activation bits.  B = 0 zero-fills the gradients here.  WHVI_OK with ln.grid.x = 0: nothing to launch.
+inline int mlp_apply_bwd_check(MlpBwdLaunch &ln, void *grad_w_in, void *grad_w_mid, void *grad_w_out, void *grad_b, void *grad_x,
+                               void *work, int64_t work_floats, const void *g, const void *x, int32_t first, const void *w_in,
+                               const void *b_in, int32_t n_mid, const void *s1, const void *s2, const void *u,
+                               const void *b_mid, int32_t mid_bias, const void *w_out, int64_t S, int64_t B, int32_t log2d,
+                               int32_t bits, const char *bits_name, hipStream_t st)
 {
-    g_err[0] = 0;
+    ln.grid = dim3(0);
     if (S < 0 || B < 0) return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: negative size%s", "");
     if (first != WHVI_MLP_FIRST_COLUMN && first != WHVI_MLP_FIRST_K4 && first != WHVI_MLP_FIRST_K8)
         return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: unknown first-layer kind%s %lld", "", first);
     if (!mlp_bwd_supported(first, n_mid, log2d))
         return fail(WHVI_ERR_SIZE, "whvi_mlp_apply_bwd: unsupported network%s (n_mid = %lld, log2(D) = %lld; see "
                     "whvi_mlp_apply_bwd_supported)", "", n_mid, log2d);
-    if (relu & ~((1 << (n_mid + 1)) - 1)) return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: unknown relu bits%s 0x%llx", "", relu);
+    if (bits & ~((1 << (n_mid + 1)) - 1))
+        return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: unknown %s bits 0x%llx", bits_name, bits);
     if (mid_bias & ~((1 << n_mid) - 1))
         return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: unknown mid_bias bits%s 0x%llx", "", mid_bias);
     if (S == 0) return WHVI_OK;
@@ -296,7 +392,6 @@ inline int mlp_apply_bwd_dispatch(void *grad_w_in, void *grad_w_mid, void *grad_
     if (work_floats < need)
         return fail(WHVI_ERR_ARG, "whvi_mlp_apply_bwd: workspace of%s %lld floats, %lld needed (whvi_mlp_apply_bwd_workspace)", "",
                     work_floats, need);
-    hipStream_t st = (hipStream_t)stream;
     const uint32_t D = 1u << log2d;
     if (B == 0) {                                          // no rows: every gradient is an empty sum
         const int64_t kin = first;
@@ -308,39 +403,11 @@ inline int mlp_apply_bwd_dispatch(void *grad_w_in, void *grad_w_mid, void *grad_
     }
     const int64_t slab_rows = (B + n_slabs - 1) / n_slabs;
     if (n_slabs * S >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_mlp_apply_bwd: too many blocks%s", "");
-    const size_t lds = (size_t)mlp_lds_bytes(first, n_mid, log2d) + 16;
-    const dim3 grid((unsigned)(n_slabs * S));
-#define WHVI_MLPB(L, K, N)                                                                                      \
-    do {                                                                                                        \
-        if constexpr (mlp_lds_bytes(K, N, L) <= MLP_MAX_LDS) {                                                  \
-            note_launch<float>("mlp_apply_bwd_kernel", L, K, N);                                                \
-            hipLaunchKernelGGL((mlp_apply_bwd_kernel<float, L, K, N>), grid, dim3(256), lds, st, (float *)work,   \
-                               (float *)grad_x, (const float *)g, (const float *)x, (const float *)w_in,        \
-                               (const float *)b_in, (const float *)s1, (const float *)s2, (const float *)u,     \
-                               (const float *)b_mid, (const float *)w_out, (uint32_t)S, (uint32_t)B,            \
-                               (uint32_t)mid_bias, (uint32_t)relu, (uint32_t)slab_rows, (uint32_t)n_slabs);     \
-        }                                                                                                       \
-    } while (0)
-#define WHVI_MLPB_K(L, K)                                                                                       \
-    if (n_mid == 1) WHVI_MLPB(L, K, 1); else WHVI_MLPB(L, K, 2);
-#define WHVI_CASE(L)                                                                                            \
-    case L:                                                                                                     \
-        if (first == 1) { WHVI_MLPB_K(L, 1) } else if (first == 4) { WHVI_MLPB_K(L, 4) } else { WHVI_MLPB_K(L, 8) } \
-        break;
-    switch (log2d) {
-        WHVI_CASE(6) WHVI_CASE(7) WHVI_CASE(8) WHVI_CASE(9) WHVI_CASE(10)
-    default: break;
-    }
-#undef WHVI_CASE
-#undef WHVI_MLPB_K
-#undef WHVI_MLPB
-    int rc = after_launch("mlp_apply_bwd");
-    if (rc != WHVI_OK) return rc;
-    const int64_t total = S * (first + n_mid + 1) * (int64_t)D + (1 + n_mid) * (int64_t)D + 1;
-    hipLaunchKernelGGL(mlp_apply_bwd_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)grad_w_in,
-                       (float *)grad_w_mid, (float *)grad_w_out, (float *)grad_b, (const float *)work, (uint32_t)S,
-                       (uint32_t)n_slabs, (uint32_t)first, (uint32_t)n_mid, (uint32_t)log2d);
-    return after_launch("mlp_apply_bwd (finish)");
+    ln.lds = (size_t)mlp_lds_bytes(first, n_mid, log2d) + 16;
+    ln.grid = dim3((unsigned)(n_slabs * S));
+    ln.slab_rows = (uint32_t)slab_rows;
+    ln.n_slabs = (uint32_t)n_slabs;
+    return WHVI_OK;
 }
 
 inline int64_t mlp_apply_bwd_workspace(int64_t S, int64_t B, int32_t first, int32_t n_mid, int32_t log2d)

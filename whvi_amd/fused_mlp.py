@@ -1,16 +1,20 @@
 """One-launch passes of a WHVI regression network of the canonical shape: the predictive pass (opt-in:
 ``WHVINetwork.set_fused_inference()``) and the training pass, forward + backward (opt-in: ``WHVINetwork.set_fused_training()``).
 
-The reference's network -- ``[WHVILinear(n_in, D), ReLU, WHVILinear(D, D), ReLU, WHVILinear(D, 1)]`` (src/evaluation.py:79-85,
-the toy notebook's 1 -> 128 -> 128 -> 1, BASELINE config 4's 3 -> 1024 -> 1024 -> 1) -- runs on the batched GPU route as three
-launches that write and re-read two ``(S, B, D)`` activations.  ``whvi_mlp_apply_f32`` (whvi_amd/csrc/mlp_apply.hpp) keeps
-each row's hidden vector on chip instead: it reads ``x`` and writes ``y``.  Every layer's operands come from the same
-``_mc_operands`` the batched route's ``forward_mc`` calls, in the same order, so the draws are the same; the kernel repeats
-the arithmetic of the launches it replaces, so the result is bit-identical to ``forward_batched`` without the flag.
+The reference's networks -- ``[WHVILinear(n_in, D), act, WHVILinear(D, D), act, WHVILinear(D, 1)]``: the UCI networks with
+``act = nn.ReLU`` (src/evaluation.py:79-85), the toy notebook's WHVI models 1 -> 128 -> 128 -> 1 with ``act = nn.Sigmoid``
+(experiments/Toy example.ipynb), BASELINE config 4's 3 -> 1024 -> 1024 -> 1 with ReLU -- run on the batched GPU route as three
+launches that write and re-read two ``(S, B, D)`` activations (plus one torch pass per sigmoid).  ``whvi_mlp_apply_f32``
+(whvi_amd/csrc/mlp_apply.hpp) keeps each row's hidden vector on chip instead: it reads ``x`` and writes ``y``.  Each boundary
+carries ``nn.ReLU``, ``nn.Sigmoid``, ``nn.Tanh`` or nothing, one activation kind per network (sigmoid and tanh through
+``whvi_mlp_apply_act_f32``, ATen's float formulas).  Every layer's operands come from the same ``_mc_operands`` the batched
+route's ``forward_mc`` calls, in the same order, so the draws are the same; the kernel repeats the arithmetic of the launches
+it replaces, so the result is bit-identical to ``forward_batched`` without the flag.
 
 Training: ``MLPApplyFunction`` wraps the same launch in an autograd Function that saves only its inputs.  Its backward is
 one call of ``whvi_mlp_apply_bwd_f32`` (whvi_amd/csrc/mlp_apply_bwd.hpp), which recomputes every row's hidden vectors with the
-forward's arithmetic -- hence the batched route's ReLU masks -- and applies that route's backward formulas; the batch sums run
+forward's arithmetic -- hence the batched route's ReLU masks, or the sigmoid / tanh outputs torch's backward formulas read --
+and applies that route's backward formulas; the batch sums run
 in a fixed order (bit-identical gradients on every run).  They differ from the batched route's gradients only by summation
 order; the loss is bit-identical.  The gradient w.r.t. each square layer's diagonal is chained to ``u``, ``s1`` and ``s2`` by
 small torch ops, and autograd continues through ``_mc_operands`` to the parameters.  There is no double backward.
@@ -39,23 +43,34 @@ class Plan(NamedTuple):
     last: nn.Module                  # transposed WHVIColumnMatrix (D -> 1)
     layers: List[nn.Module]          # the WHVILinear modules in order (their _mc_kl is cleared like forward_batched does)
     D: int
-    relu: int                        # bit 0: ReLU behind the first layer, bit 1 + m: behind square layer m
+    relu: int                        # ReLU networks: act_bits; sigmoid / tanh networks: 0
+    act: str = "relu"                # the activation kind at every activated boundary: "relu", "sigmoid" or "tanh"
+    act_bits: int = 0                # bit 0: the activation behind the first layer, bit 1 + m: behind square layer m
+
+
+_ACTS = {nn.ReLU: "relu", nn.Sigmoid: "sigmoid", nn.Tanh: "tanh"}      # the activations the passes fuse
 
 
 def match(net) -> Union[Plan, str]:
     """The plan of the one-launch pass for ``net``'s module list, or why it has none."""
     mods = list(net.sequential)
     layers, relu_after = [], []
+    act, act_mod = None, None
     for i, m in enumerate(mods):
-        if type(m) is nn.ReLU:
+        kind = _ACTS.get(type(m))
+        if kind is not None:
+            name = type(m).__name__
+            if act is not None and kind != act:
+                return f"module {i}: nn.{name} after nn.{act_mod}: the fused passes take one activation kind per network"
             if not layers or relu_after[-1] or i == len(mods) - 1:
-                return f"module {i}: an nn.ReLU is only fused between two WHVI layers (one per boundary)"
+                return f"module {i}: an nn.{name} is only fused between two WHVI layers (one per boundary)"
+            act, act_mod = kind, name
             relu_after[-1] = True
         elif isinstance(m, WHVILinear):
             layers.append(m)
             relu_after.append(False)
         else:
-            return f"module {i}: {type(m).__name__} is neither WHVILinear nor nn.ReLU"
+            return f"module {i}: {type(m).__name__} is neither WHVILinear nor nn.ReLU / nn.Sigmoid / nn.Tanh"
     if len(layers) < 3:
         return f"{len(layers)} WHVI layers: the fused pass needs a first layer, 1 .. 4 square layers and an output layer"
     if len(layers) - 2 > 4:
@@ -92,10 +107,11 @@ def match(net) -> Union[Plan, str]:
         return f"output layer: width {last.D} differs from the hidden width {D}"
     if not _hip.mlp_apply_supported(kind, len(mids), D):
         return f"hidden width {D} with {len(mids)} square layers is outside whvi_mlp_apply's range"
-    relu = 0
+    bits = 0
     for i, r in enumerate(relu_after[:-1]):
-        relu |= (1 << i) if r else 0
-    return Plan(first, kind, n_in, mids, last, layers, D, relu)
+        bits |= (1 << i) if r else 0
+    act = act or "relu"
+    return Plan(first, kind, n_in, mids, last, layers, D, bits if act == "relu" else 0, act, bits)
 
 
 def _params(p: Plan):
@@ -136,10 +152,10 @@ class MLPApplyFunction(torch.autograd.Function):
     (the mean) taking the sum over the samples, as ``DiagApplyFunction.backward`` does.  First order only."""
 
     @staticmethod
-    def forward(ctx, x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias, relu):
-        ctx.mid_bias, ctx.relu = int(mid_bias), int(relu)
+    def forward(ctx, x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias, relu, act="relu"):
+        ctx.mid_bias, ctx.relu, ctx.act = int(mid_bias), int(relu), act
         ctx.save_for_backward(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out)
-        return _hip.mlp_apply(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias=mid_bias, relu=relu)
+        return _hip.mlp_apply(x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out, mid_bias=mid_bias, relu=relu, act=act)
 
     @staticmethod
     def backward(ctx, g):
@@ -149,7 +165,7 @@ class MLPApplyFunction(torch.autograd.Function):
         x, w_in, b_in, s1, s2, u, b_mid, w_out, b_out = ctx.saved_tensors
         need = ctx.needs_input_grad
         gw_in, gw_mid, gw_out, gb, gx = _hip.mlp_apply_bwd(g, x, w_in, b_in, s1, s2, u, b_mid, w_out, mid_bias=ctx.mid_bias,
-                                                          relu=ctx.relu, need_grad_x=need[0])
+                                                          relu=ctx.relu, need_grad_x=need[0], act=ctx.act)
         n_mid, S, D = gw_mid.shape
         grad_x = gx.sum(dim=0) if gx is not None else None
         grad_b_in = gb[:D].view(b_in.shape) if b_in is not None else None
@@ -165,7 +181,7 @@ class MLPApplyFunction(torch.autograd.Function):
             grad_u = torch.cat((k_u.sum(dim=1, keepdim=True), k_u), dim=1)        # row 0 (the mean) takes the sum
             grad_s1 = (gw_mid * (Dd * (u0 * c) + Dd * (uk * c))).sum(dim=1)
             grad_s2 = (gw_mid * (a * Dd * (u0 + uk))).sum(dim=1)
-        return grad_x, gw_in, grad_b_in, grad_s1, grad_s2, grad_u, grad_b_mid, gw_out, grad_b_out, None, None
+        return grad_x, gw_in, grad_b_in, grad_s1, grad_s2, grad_u, grad_b_mid, gw_out, grad_b_out, None, None, None
 
 
 def _bias(w) -> Optional[torch.Tensor]:
@@ -207,9 +223,10 @@ def run(net, p: Plan, x: torch.Tensor, n_samples: int, training: bool = False) -
     if mid_bias:
         b_mid = torch.stack([m.bias.reshape(-1) if m.bias is not None else torch.zeros_like(m.s1) for m in p.mids])
     if training:
-        y = MLPApplyFunction.apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias, p.relu)
+        y = MLPApplyFunction.apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias, p.act_bits, p.act)
     else:
-        y = _hip.mlp_apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias=mid_bias, relu=p.relu)
+        y = _hip.mlp_apply(xin, w_in, _bias(first), s1, s2, u, b_mid, w_out, _bias(p.last), mid_bias=mid_bias, relu=p.act_bits,
+                           act=p.act)
     total = None
     if all(torch.is_tensor(k) for k in kls):
         for k in kls:

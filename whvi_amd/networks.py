@@ -91,22 +91,26 @@ class WHVINetwork(nn.Module, WHVI):
 
     def set_fused_inference(self, on: bool = True):
         """Opt in to the one-launch predictive pass (``whvi_amd.fused_mlp``, ``whvi_mlp_apply_f32``) for networks of the
-        reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4 ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, ``nn.ReLU`` between
-        them or not; n_in <= 8.  ``forward_batched`` then makes the same draws in the same order and computes the same values
-        (bit for bit) without materialising the ``(S, batch, D)`` activations, whenever no autograd graph is wanted (grad mode
-        off, or nothing of the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before
-        (a pass that wants a graph takes the fused route only with ``set_fused_training``).  ``eval_model`` evaluates under
-        ``torch.no_grad()`` while the flag is on."""
+        reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4 ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, with or without an
+        activation at each boundary: ``nn.ReLU``, ``nn.Sigmoid`` or ``nn.Tanh``, one kind per network (the smooth ones through
+        ``whvi_mlp_apply_act_f32``, with ATen's float formulas); n_in <= 8.  ``forward_batched`` then makes the same draws in
+        the same order and computes the same values without materialising the ``(S, batch, D)`` activations (bit for bit for
+        ReLU networks; DESIGN.md 5.3e for the smooth ones), whenever no autograd graph is wanted (grad mode off, or nothing of
+        the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before (a pass that wants
+        a graph takes the fused route only with ``set_fused_training``).  ``eval_model`` evaluates under ``torch.no_grad()``
+        while the flag is on."""
         self.fused_inference = bool(on)
         return self
 
     def set_fused_training(self, on: bool = True):
         """Opt in to the trainable one-launch pass (``whvi_amd.fused_mlp.MLPApplyFunction``: ``whvi_mlp_apply_f32`` forward,
-        ``whvi_mlp_apply_bwd_f32`` backward) for the networks ``set_fused_inference`` covers, with at most 2 square layers and
-        D <= 1024.  A ``forward_batched`` call that wants an autograd graph then makes the same draws, returns the same values
-        (bit for bit) and saves no ``(S, batch, D)`` activation; its gradients differ from the batched route's only by
-        summation order, and are the same on every run.  No double backward (``create_graph=True`` raises).  Every other call
-        takes the route it takes without this flag; the two flags are independent."""
+        ``whvi_mlp_apply_bwd_f32`` backward; ``whvi_mlp_apply_act_f32`` / ``whvi_mlp_apply_act_bwd_f32`` for sigmoid and tanh
+        networks, whose backward applies torch's formulas to the recomputed activation outputs) for the networks
+        ``set_fused_inference`` covers, with at most 2 square layers and D <= 1024.  A ``forward_batched`` call that wants an
+        autograd graph then makes the same draws, returns the forward values ``set_fused_inference`` returns and saves no
+        ``(S, batch, D)`` activation; its gradients differ from the batched route's only by summation order, and are the same on
+        every run.  No double backward (``create_graph=True`` raises).  Every other call takes the route it takes without this
+        flag; the two flags are independent."""
         self.fused_training = bool(on)
         return self
 
