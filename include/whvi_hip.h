@@ -417,6 +417,26 @@ int whvi_mlp_apply_act_bwd_f32(void *grad_w_in, void *grad_w_mid, void *grad_w_o
                                const void *b_mid, int32_t mid_bias, const void *w_out, int64_t S, int64_t B, int32_t log2d,
                                int32_t act, int32_t act_bits, void *stream);
 
+/* The predictive pass of a WHVI regression network whose square layers are FASTFOOD layers (WHVILinear(D, D, mode="fastfood"):
+ * x -> s1 * H(g_k * H(s2 * x)), H the unnormalised Walsh-Hadamard transform) for all Monte-Carlo samples in ONE launch that
+ * keeps each row's hidden vector on chip.  f32; per (s, b):
+ *     h = first(x[b, :]; s) (+ b_in) (act if bit 0 of act_bits)                       -- as whvi_mlp_apply_f32
+ *     h = s1[m] * H(g[m, s] * H(s2[m] * h)) (+ b_mid[m] if bit m of mid_bias) (act if bit 1 + m of act_bits)
+ *     y[s, b] = row_dot(h, w_out[s]) (+ b_out[0])                                      -- as whvi_mlp_apply_f32
+ * Each square layer repeats whvi_fused_shs_f32 (axis = COL, a = s1, b = g per sample, c = s2) and a separate bias add: the
+ * result is bit-identical to that launch plus the add.  There is no row-poison rule: non-finite values propagate through the
+ * butterflies.  first, x, w_in, b_in, w_out, b_out, act (WHVI_MLP_ACT_*) and act_bits are those of whvi_mlp_apply_act_f32;
+ * s1, s2, b_mid (n_mid, D), g (n_mid, S, D).  y (S, B) must not overlap any input; every pointer 16-byte aligned.
+ * Supported: log2d in [6, 11], n_mid in [1, 4] and the operands of one sample in 64 KiB of LDS:
+ * 4 * 2^log2d * (K + 2 + 4 n_mid) <= 65536 bytes (K = 1 for the column layer) -- whvi_mlp_fastfood_apply_supported(first,
+ * n_mid, log2d) returns 1 exactly then; otherwise the call returns WHVI_ERR_SIZE.  Every argument check runs before any
+ * launch.  No allocation, no synchronisation: capture-safe. */
+int whvi_mlp_fastfood_apply_supported(int32_t first, int32_t n_mid, int32_t log2d);
+int whvi_mlp_fastfood_apply_f32(void *y, const void *x, int32_t first, const void *w_in, const void *b_in, int32_t n_mid,
+                                const void *s1, const void *s2, const void *g, const void *b_mid, int32_t mid_bias,
+                                const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t act,
+                                int32_t act_bits, void *stream);
+
 /* whvi_reparam_kl_f32 with the eps draw inside the kernel: Philox4x32-10 + Box-Muller, one standard
  * normal per (matrix, sample, element), written to eps_out (J, S, D) for the backward pass / inspection.  The
  * generator state is three 64-bit words in DEVICE memory, state = {seed, launch offset, scratch (must be 0)}; the

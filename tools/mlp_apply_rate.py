@@ -6,8 +6,11 @@ launch, WHVINetwork.set_fused_inference) against the batched three-launch route,
 For every shape the two routes' outputs are first checked to be torch.equal for the same generator state; only then are they
 timed, alternately (route A, route B, route A, ...) with HIP events around `--iters` back-to-back passes, `--repeats` times.
 Prints one JSON object: per shape and route the median / min / max milliseconds per pass over the repeats.
+``--fastfood``: the square layer is WHVILinear(D, D, mode="fastfood") -- the fused route is then one whvi_mlp_fastfood_apply
+launch (whvi_amd/fused_fastfood.py), the batched route small_k_apply / fused_shs / torch bias add / row_dot.  ``--no-bias``:
+every layer without its bias.
 
-    python tools/mlp_apply_rate.py [--iters 20] [--repeats 7] [--shapes toy,uci,config4]"""
+    python tools/mlp_apply_rate.py [--iters 20] [--repeats 7] [--shapes toy,uci,config4] [--fastfood] [--no-bias]"""
 import argparse
 import json
 import os
@@ -31,16 +34,19 @@ SHAPES = {                      # name: (n_in, D, batch, samples)
 ACTS = {"relu": nn.ReLU, "sigmoid": nn.Sigmoid, "tanh": nn.Tanh}    # --act: the activation at both boundaries
 
 
-def _net(n_in, D, act="relu"):
+def _net(n_in, D, act="relu", fastfood=False, bias=True):
     from whvi_amd.layers import WHVILinear
     from whvi_amd.networks import WHVIRegression
     torch.manual_seed(0)
-    net = WHVIRegression([WHVILinear(n_in, D, bias=True), ACTS[act](), WHVILinear(D, D, bias=True), ACTS[act](),
-                          WHVILinear(D, 1, bias=True)])
+    net = WHVIRegression([WHVILinear(n_in, D, bias=bias), ACTS[act](),
+                          WHVILinear(D, D, bias=bias, mode="fastfood" if fastfood else "reference"), ACTS[act](),
+                          WHVILinear(D, 1, bias=bias)])
     with torch.no_grad():
         for name, p in net.named_parameters():
             if name.endswith(("g_mu", "s1", "s2", "bias")):
                 p.normal_(0.0, 0.3)
+        if fastfood:
+            net.sequential[2].weight_submodule.s1.mul_(1.0 / D)    # the two unnormalised transforms grow a row by D
     return net.cuda().eval()
 
 
@@ -61,13 +67,16 @@ def main():
     ap.add_argument("--act", choices=sorted(ACTS), default="relu", help="the activation at both boundaries (sigmoid: the toy "
                     "notebook's own WHVI model at the toy shape)")
     ap.add_argument("--shapes", default="toy,uci,config4")
+    ap.add_argument("--fastfood", action="store_true", help="a fastfood square layer (whvi_mlp_fastfood_apply)")
+    ap.add_argument("--no-bias", action="store_true", help="every layer without its bias")
     args = ap.parse_args()
     from whvi_amd import _hip
     from whvi_amd.graphs import GraphedPredictor
-    result = {"gpu": torch.cuda.get_device_name(0), "act": args.act, "iters": args.iters, "repeats": args.repeats, "shapes": {}}
+    result = {"gpu": torch.cuda.get_device_name(0), "act": args.act, "fastfood": args.fastfood, "bias": not args.no_bias,
+              "iters": args.iters, "repeats": args.repeats, "shapes": {}}
     for name in args.shapes.split(","):
         n_in, D, B, S = SHAPES[name]
-        net = _net(n_in, D, args.act)
+        net = _net(n_in, D, args.act, args.fastfood, not args.no_bias)
         x = torch.randn(B, n_in, device="cuda")
         outs = []
         for fused in (False, True):
@@ -76,7 +85,8 @@ def main():
             with torch.no_grad():
                 outs.append(net.forward_batched(x, S))
         kernel = _hip.last_kernel()
-        if not (kernel.startswith(("whvi::mlp_apply_kernel<", "whvi::mlp_smooth_apply_kernel<")) and torch.equal(outs[0], outs[1])):
+        want = ("whvi::mlp_fastfood_apply_kernel<",) if args.fastfood else ("whvi::mlp_apply_kernel<", "whvi::mlp_smooth_apply_kernel<")
+        if not (kernel.startswith(want) and torch.equal(outs[0], outs[1])):
             raise SystemExit(f"{name}: the fused pass ({kernel}) does not reproduce the three-launch route")
         del outs
         routes = {}

@@ -117,6 +117,11 @@ def _declare_f3(lib):
     lib.whvi_mlp_apply_act_bwd_f32.restype = ctypes.c_int
     lib.whvi_mlp_apply_act_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64,
                                                i64, i32, i32, i32, vp]
+    lib.whvi_mlp_fastfood_apply_supported.restype = ctypes.c_int
+    lib.whvi_mlp_fastfood_apply_supported.argtypes = [i32, i32, i32]
+    lib.whvi_mlp_fastfood_apply_f32.restype = ctypes.c_int
+    lib.whvi_mlp_fastfood_apply_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32,
+                                                vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -681,6 +686,48 @@ def mlp_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: t
                                               s1.data_ptr(), s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias),
                                               w_out.data_ptr(), ptr(b_out), S, B, D.bit_length() - 1, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply")
+    return y
+
+
+def mlp_fastfood_apply_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_fastfood_apply_supported`` (include/whvi_hip.h) without the library: first-layer kind 1 / 4 / 8,
+    1 .. 4 fastfood square layers, D = 64 .. 2048 a power of two, and one sample's operands -- 4 D (K + 2 + 4 n_mid) bytes
+    (s1, s2, g_k and the bias per square layer) -- within 64 KiB of LDS."""
+    return (first in (MLP_FIRST_COLUMN, MLP_FIRST_K4, MLP_FIRST_K8) and 1 <= n_mid <= 4 and 64 <= d <= 2048
+            and (d & (d - 1)) == 0 and 4 * d * (first + 2 + 4 * n_mid) <= 65536)
+
+
+def mlp_fastfood_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor, g: torch.Tensor, b_mid,
+                       w_out: torch.Tensor, b_out, *, mid_bias: int = 0, act_bits: int = 0, act: str = "relu") -> torch.Tensor:
+    """One launch: the predictive pass of a WHVI regression network with fastfood square layers for all MC samples -- y (S, B);
+    see whvi_mlp_fastfood_apply_f32 in include/whvi_hip.h.  x, w_in, b_in, w_out, b_out, ``act`` and ``act_bits`` as
+    ``mlp_apply``; s1, s2 (n_mid, D); g (n_mid, S, D), every sample's g_k; b_mid (n_mid, D) or None (``mid_bias`` bit m:
+    square layer m has a bias)."""
+    code = _mlp_act(act)
+    S, D = w_out.shape
+    n_mid = s1.shape[0]
+    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
+    if not mlp_fastfood_apply_supported(first, n_mid, D):
+        raise RuntimeError(f"mlp_fastfood_apply: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
+    ops = (x, w_in, s1, s2, g, w_out) + tuple(t for t in (b_in, b_mid, b_out) if t is not None)
+    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
+        raise RuntimeError("mlp_fastfood_apply: float32 CUDA tensors on one device only")
+    B = x.shape[0]
+    if (tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D) or tuple(s1.shape) != (n_mid, D)
+            or tuple(s2.shape) != (n_mid, D) or tuple(g.shape) != (n_mid, S, D)
+            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)
+            or (b_out is not None and b_out.numel() != 1)):
+        raise RuntimeError("mlp_fastfood_apply: operand shapes do not match")
+    x, w_in, s1, s2, g, w_out = (_aligned(t) for t in (x, w_in, s1, s2, g, w_out))
+    b_in, b_mid, b_out = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid, b_out))
+    y = torch.empty((S, B), dtype=torch.float32, device=x.device)
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    with _OnDevice(x.device):
+        rc = lib().whvi_mlp_fastfood_apply_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
+                                               s1.data_ptr(), s2.data_ptr(), g.data_ptr(), ptr(b_mid), int(mid_bias),
+                                               w_out.data_ptr(), ptr(b_out), S, B, D.bit_length() - 1, code, int(act_bits),
+                                               _stream(x))
+    _check(rc, "whvi_mlp_fastfood_apply")
     return y
 
 

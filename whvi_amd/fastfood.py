@@ -162,11 +162,16 @@ class WHVIFastfoodMatrix(nn.Module):
         H = build_H(self.D, self.g_mu.device).to(self.g_mu.dtype)
         return self.s1.unsqueeze(1) * (H @ (g.unsqueeze(1) * (H * self.s2.unsqueeze(0))))
 
+    def _mc_operands(self, n_samples):
+        """g (S, D): every sample's diagonal for one batched pass -- row k from row k of one ``randn(n_samples, D)`` draw (the
+        draw of ``forward_mc``; shared with the one-launch predictive pass, ``whvi_amd.fused_fastfood``)."""
+        eps = torch.randn(n_samples, self.D, device=self.g_mu.device)
+        return self.g_mu + self.g_sigma * eps
+
     def forward_mc(self, x, n_samples):
         """(batch, D) or (n_samples, batch, D) -> (n_samples, batch, D); sample k uses row k of one
         ``randn(n_samples, D)`` draw."""
-        eps = torch.randn(n_samples, self.D, device=self.g_mu.device)
-        g = self.g_mu + self.g_sigma * eps                                        # (S, D)
+        g = self._mc_operands(n_samples)                                          # (S, D)
         if x.dim() == 2:
             # a (batch, D) input shared by all samples: read by every sample straight from the caches, never expanded
             batch = x.size(0)

@@ -1,0 +1,130 @@
+"""The one-launch predictive pass of a WHVI regression network whose square layers are fastfood layers (opt-in:
+``WHVINetwork.set_fused_inference()``, the flag of ``whvi_amd.fused_mlp``).
+
+A fastfood network -- ``[WHVILinear(n_in, D), act, WHVILinear(D, D, mode="fastfood"), act, ..., WHVILinear(D, 1)]`` -- has the
+outer shape of ``fused_mlp``'s networks, but each square layer applies the paper's operator ``s1 * H(g_k * H(s2 * h))``
+(``whvi_amd.fastfood``) instead of a diagonal.  On the batched route every layer moves the ``(S, batch, D)`` activations through
+HBM: ``small_k_apply`` (or the column layer's product) writes them, ``fused_shs`` reads and writes them, a torch add per bias and
+a torch pass per activation that no launch folds read and write them, ``row_dot`` reads them.  ``whvi_mlp_fastfood_apply_f32``
+(whvi_amd/csrc/mlp_fastfood_apply.hip) keeps each row in registers, runs both transforms of every square layer there, and
+reads ``x`` and writes ``y`` only.  Every layer's operands come from the ``_mc_operands`` the batched route's ``forward_mc``
+calls, in module order, so the draws are the same; the kernel repeats the arithmetic of the launches it replaces (the fused
+kernel's butterfly network, the bias as its own add), so the result is bit-identical to ``forward_batched`` without the flag.
+
+``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples)`` adds the checks of one call, ``run``
+makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the caller
+then takes the batched route.  There is no backward: a call that wants an autograd graph is refused."""
+from typing import List, NamedTuple, Union
+
+import torch
+import torch.nn as nn
+
+from whvi_amd import _hip
+from whvi_amd.fastfood import WHVIFastfoodMatrix
+from whvi_amd.fused_mlp import _act_bits, _first_layer, _output_layer, _scan
+from whvi_amd.weights import WHVIColumnMatrix, WHVISquarePow2Matrix, WHVIStackedMatrix
+
+__all__ = ["Plan", "match", "plan", "run"]
+
+
+class Plan(NamedTuple):
+    first: nn.Module                 # WHVIStackedMatrix (K = D_in = 4 / 8) or WHVIColumnMatrix (n_in = 1)
+    kind: int                        # _hip.MLP_FIRST_K4 / _K8 / _COLUMN
+    n_in: int
+    mids: List[nn.Module]            # WHVIFastfoodMatrix, 1 .. 4 of them
+    last: nn.Module                  # transposed WHVIColumnMatrix (D -> 1)
+    layers: List[nn.Module]          # the WHVILinear modules in order
+    D: int
+    act: str                         # the activation kind at every activated boundary: "relu", "sigmoid" or "tanh"
+    act_bits: int                    # bit 0: the activation behind the first layer, bit 1 + m: behind square layer m
+
+
+def match(net) -> Union[Plan, str]:
+    """The plan of the one-launch fastfood pass for ``net``'s module list, or why it has none."""
+    scan = _scan(net)
+    if isinstance(scan, str):
+        return scan
+    layers, act_after, act, _ = scan
+    subs = [m.weight_submodule for m in layers]
+    first, mids, last = subs[0], subs[1:-1], subs[-1]
+    for i in (0, len(subs) - 1):
+        w = subs[i]
+        if not isinstance(w, (WHVIStackedMatrix, WHVIColumnMatrix)):
+            return f"layer {i}: {type(w).__name__} is not a stacked or column WHVI matrix"
+        if getattr(w, "hip_apply", True) is False:
+            return f"layer {i}: faithful dataflow is on (hip_apply = False)"
+    kinds = {type(w).__name__ for w in mids}
+    if not any(isinstance(w, WHVIFastfoodMatrix) for w in mids):
+        return "no fastfood square layer (mode='fastfood'): the reference-mode networks are fused_mlp's"
+    for j, w in enumerate(mids):
+        if isinstance(w, WHVISquarePow2Matrix):
+            return f"layer {1 + j}: WHVISquarePow2Matrix among fastfood layers: the pass takes one square layer kind " \
+                   f"({' and '.join(sorted(kinds))} mixed)"
+        if not isinstance(w, WHVIFastfoodMatrix):
+            return f"layer {1 + j}: {type(w).__name__} is not a fastfood square layer"
+    head = _first_layer(first)
+    if isinstance(head, str):
+        return head
+    D, kind, n_in = head
+    for j, w in enumerate(mids):
+        if w.D != D:
+            return f"layer {1 + j}: width {w.D} differs from the first layer's {D}"
+    reason = _output_layer(last, D)
+    if reason is not None:
+        return reason
+    if not _hip.mlp_fastfood_apply_supported(kind, len(mids), D):
+        return f"hidden width {D} with {len(mids)} fastfood layers is outside whvi_mlp_fastfood_apply's range"
+    return Plan(first, kind, n_in, list(mids), last, layers, D, act or "relu", _act_bits(act_after))
+
+
+def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
+    """``match(net)`` plus the checks of this call: float32 CUDA input and parameters on x's device, sizes, and no autograd
+    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad)."""
+    p = match(net)
+    if isinstance(p, str):
+        return p
+    if x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != p.n_in:
+        return f"input: needs a float32 CUDA (batch, {p.n_in}) tensor"
+    params = [t for m in p.layers for t in m.parameters()]
+    if any(t.device != x.device or t.dtype != torch.float32 for t in params):
+        return "parameters: float32 on the input's device only"
+    S, B = int(n_samples), x.shape[0]
+    if S < 1 or S * B >= 2 ** 32:
+        return f"{S} samples x {B} rows: outside 1 .. 2^32 - 1 rows"
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
+        return "an autograd graph is wanted (the fused fastfood pass has no backward)"
+    return p
+
+
+def _bias(w):
+    return None if w.bias is None else w.bias.reshape(-1)
+
+
+def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
+    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch.
+    Returns ``(batch, 1, S)`` in forward_batched's layout; sets ``net._pass_kl`` as the batched route does -- to None, because
+    fastfood layers report no in-pass KL."""
+    S = int(n_samples)
+    first = p.first
+    w_in, _ = first._mc_operands(S)                                 # (S, D, K) or (S, D)
+    if p.kind == _hip.MLP_FIRST_COLUMN:
+        xin = x
+    else:
+        xin = torch.zeros((x.shape[0], first.D_in), device=x.device)   # forward_mc's x_padded
+        xin[:, :first.n_in] = x
+    gs = [w._mc_operands(S) for w in p.mids]                        # (S, D) each
+    w_out, _ = p.last._mc_operands(S)                               # (S, D)
+    for m in p.layers:
+        m._mc_kl = None
+        m.weight_submodule._mc_kl = None
+    s1 = torch.stack([w.s1 for w in p.mids])
+    s2 = torch.stack([w.s2 for w in p.mids])
+    g = torch.stack(gs)
+    mid_bias = sum(1 << j for j, w in enumerate(p.mids) if w.bias is not None)
+    b_mid = None
+    if mid_bias:
+        b_mid = torch.stack([w.bias.reshape(-1) if w.bias is not None else torch.zeros_like(w.s1) for w in p.mids])
+    y = _hip.mlp_fastfood_apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias=mid_bias,
+                                act_bits=p.act_bits, act=p.act)
+    net._pass_kl = None
+    return y.unsqueeze(-1).permute(1, 2, 0)

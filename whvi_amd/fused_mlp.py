@@ -51,8 +51,9 @@ class Plan(NamedTuple):
 _ACTS = {nn.ReLU: "relu", nn.Sigmoid: "sigmoid", nn.Tanh: "tanh"}      # the activations the passes fuse
 
 
-def match(net) -> Union[Plan, str]:
-    """The plan of the one-launch pass for ``net``'s module list, or why it has none."""
+def _scan(net):
+    """``(layers, act_after, act, act_mod)`` of ``net``'s module list -- its WHVILinear modules, whether an activation follows
+    each, the one activation kind (or None) and its module name -- or why the fused passes cannot take that list."""
     mods = list(net.sequential)
     layers, relu_after = [], []
     act, act_mod = None, None
@@ -75,13 +76,11 @@ def match(net) -> Union[Plan, str]:
         return f"{len(layers)} WHVI layers: the fused pass needs a first layer, 1 .. 4 square layers and an output layer"
     if len(layers) - 2 > 4:
         return f"{len(layers) - 2} square layers: at most 4"
-    subs = [m.weight_submodule for m in layers]
-    for i, w in enumerate(subs):
-        if not isinstance(w, (WHVIStackedMatrix, WHVIColumnMatrix, WHVISquarePow2Matrix)):
-            return f"layer {i}: {type(w).__name__} (mode='fastfood'?) is not a reference-mode WHVI matrix"
-        if getattr(w, "hip_apply", True) is False:
-            return f"layer {i}: faithful dataflow is on (hip_apply = False)"
-    first, mids, last = subs[0], subs[1:-1], subs[-1]
+    return layers, relu_after, act, act_mod
+
+
+def _first_layer(first):
+    """``(D, kind, n_in)`` of a first layer the fused passes take, or why not."""
     if isinstance(first, WHVIStackedMatrix):
         if first.D_in not in (4, 8):
             return f"first layer: {first.n_in} inputs pad to K = {first.D_in} (4 or 8 only)"
@@ -94,6 +93,42 @@ def match(net) -> Union[Plan, str]:
             return f"first layer: hidden width {D} is not a power of two"
     else:
         return f"first layer: {type(first).__name__} is neither a stacked (K = 4 / 8) nor a column (n_in = 1) WHVI matrix"
+    return D, kind, n_in
+
+
+def _output_layer(last, D):
+    """Why ``last`` is not the output layer the fused passes take (None when it is)."""
+    if not (isinstance(last, WHVIColumnMatrix) and last.transposed):
+        return f"output layer: {type(last).__name__} is not WHVILinear(D, 1) (one output only)"
+    if last.D != D or last.weight_submodule.D != D:
+        return f"output layer: width {last.D} differs from the hidden width {D}"
+    return None
+
+
+def _act_bits(relu_after) -> int:
+    bits = 0
+    for i, r in enumerate(relu_after[:-1]):
+        bits |= (1 << i) if r else 0
+    return bits
+
+
+def match(net) -> Union[Plan, str]:
+    """The plan of the one-launch pass for ``net``'s module list, or why it has none."""
+    scan = _scan(net)
+    if isinstance(scan, str):
+        return scan
+    layers, relu_after, act, _ = scan
+    subs = [m.weight_submodule for m in layers]
+    for i, w in enumerate(subs):
+        if not isinstance(w, (WHVIStackedMatrix, WHVIColumnMatrix, WHVISquarePow2Matrix)):
+            return f"layer {i}: {type(w).__name__} (mode='fastfood'?) is not a reference-mode WHVI matrix"
+        if getattr(w, "hip_apply", True) is False:
+            return f"layer {i}: faithful dataflow is on (hip_apply = False)"
+    first, mids, last = subs[0], subs[1:-1], subs[-1]
+    head = _first_layer(first)
+    if isinstance(head, str):
+        return head
+    D, kind, n_in = head
     for j, w in enumerate(mids):
         if not isinstance(w, WHVISquarePow2Matrix):
             return f"layer {1 + j}: {type(w).__name__} is not a square power-of-two WHVI matrix (hidden width {D}?)"
@@ -101,15 +136,12 @@ def match(net) -> Union[Plan, str]:
             return f"layer {1 + j}: width {w.D} differs from the first layer's {D}"
         if w._diag_mode() is False:
             return f"layer {1 + j}: faithful dataflow is on (the diagonal route is switched off)"
-    if not (isinstance(last, WHVIColumnMatrix) and last.transposed):
-        return f"output layer: {type(last).__name__} is not WHVILinear(D, 1) (one output only)"
-    if last.D != D or last.weight_submodule.D != D:
-        return f"output layer: width {last.D} differs from the hidden width {D}"
+    reason = _output_layer(last, D)
+    if reason is not None:
+        return reason
     if not _hip.mlp_apply_supported(kind, len(mids), D):
         return f"hidden width {D} with {len(mids)} square layers is outside whvi_mlp_apply's range"
-    bits = 0
-    for i, r in enumerate(relu_after[:-1]):
-        bits |= (1 << i) if r else 0
+    bits = _act_bits(relu_after)
     act = act or "relu"
     return Plan(first, kind, n_in, mids, last, layers, D, bits if act == "relu" else 0, act, bits)
 

@@ -97,8 +97,10 @@ class WHVINetwork(nn.Module, WHVI):
         the same order and computes the same values without materialising the ``(S, batch, D)`` activations (bit for bit for
         ReLU networks; DESIGN.md 5.3e for the smooth ones), whenever no autograd graph is wanted (grad mode off, or nothing of
         the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before (a pass that wants
-        a graph takes the fused route only with ``set_fused_training``).  ``eval_model`` evaluates under ``torch.no_grad()``
-        while the flag is on."""
+        a graph takes the fused route only with ``set_fused_training``).  Networks whose square layers are all fastfood layers
+        (``WHVILinear(D, D, mode="fastfood")``, 1 .. 4 of them) take ``whvi_amd.fused_fastfood`` under the same flag and rules
+        (bit for bit for every activation; no trainable form).  ``eval_model`` evaluates under ``torch.no_grad()`` while the
+        flag is on."""
         self.fused_inference = bool(on)
         return self
 
@@ -142,6 +144,10 @@ class WHVINetwork(nn.Module, WHVI):
             plan = fused_mlp.plan(self, x, n_samples)
             if not isinstance(plan, str):
                 return fused_mlp.run(self, plan, x, n_samples)
+            from whvi_amd import fused_fastfood          # networks with fastfood square layers (whvi_mlp_fastfood_apply_f32)
+            plan = fused_fastfood.plan(self, x, n_samples)
+            if not isinstance(plan, str):
+                return fused_fastfood.run(self, plan, x, n_samples)
         if self.fused_training and torch.is_grad_enabled():
             from whvi_amd import fused_mlp
             plan = fused_mlp.plan(self, x, n_samples, training=True)
