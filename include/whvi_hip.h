@@ -437,6 +437,39 @@ int whvi_mlp_fastfood_apply_f32(void *y, const void *x, int32_t first, const voi
                                 const void *w_out, const void *b_out, int64_t S, int64_t B, int32_t log2d, int32_t act,
                                 int32_t act_bits, void *stream);
 
+/* Backward of whvi_mlp_fastfood_apply_f32: every parameter gradient of the network for all samples from g = dL/dy (S, B),
+ * without any saved activation -- each block recomputes its rows' hidden vectors with the forward's arithmetic (the same
+ * activation outputs and ReLU signs, bit for bit) and applies the batched route's backward formulas, last layer first:
+ *     d = g * w_out;  at fastfood layer m, with its input h, t1 = H(s2 h), t2 = H(g_k t1) recomputed:  d = act'(.) d;
+ *     grad_bias += d;  grad_s1 += d t2;  v = H(s1 d);  grad_g[k] += v t1;  w = H(g_k v);  grad_s2 += w h;  d = s2 w;
+ *     behind the first layer d = act'(.) d, then the first layer's sums as whvi_mlp_apply_bwd_f32.
+ *   act'(.) per boundary (act_bits), what the batched route runs there: sigmoid / tanh -- torch's formulas on the recomputed
+ *     output; ReLU in front of the output layer (the row dot folds it) and behind a stacked first layer (its launch folds it):
+ *     d = d * (out > 0); every other ReLU (an nn.ReLU module: behind a column first layer, between two fastfood layers):
+ *     d = 0 where out <= 0, NaN passes.
+ *   grad_w_in  : (S, D, K) = sum_b d x[b, c]   (column layer: (S, D))
+ *   grad_s1, grad_s2 : (n_mid, D), summed over samples and rows
+ *   grad_g     : (n_mid, S, D) = sum_b v t1, the gradient w.r.t. each sample's g_k
+ *   grad_w_out : (S, D) = sum_b g h_L
+ *   grad_b     : (1 + n_mid) D + 1 floats: b_in (D), b_mid (n_mid rows of D), b_out (1), summed over samples and rows --
+ *                written whatever the forward's bias pointers were
+ *   grad_x     : (S, B, K) (column layer: (S, B, 1)) = sum_n d w_in[s, n, c], or NULL to skip; the caller sums over S
+ *   work       : workspace of work_floats >= whvi_mlp_fastfood_apply_bwd_workspace(S, B, first, n_mid, log2d) floats
+ *                (WHVI_ERR_ARG otherwise).  Every block writes its partial sums there and a second, tiny launch inside the same
+ *                call adds them in ascending slab and sample order: deterministic (bit-identical on every run), no atomics.
+ * The other arguments are whvi_mlp_fastfood_apply_f32's (gk is its g).  No output and no part of the workspace may overlap an
+ * input (WHVI_ERR_OVERLAP); every pointer 16-byte aligned.  Supported: whvi_mlp_fastfood_apply_supported's range with
+ * n_mid <= 2 and log2d <= 10 -- whvi_mlp_fastfood_apply_bwd_supported(first, n_mid, log2d) returns 1 exactly then,
+ * whvi_mlp_fastfood_apply_bwd_workspace returns -1 otherwise and the call WHVI_ERR_SIZE.  Every argument check runs before any
+ * launch.  No allocation, no synchronisation: capture-safe. */
+int whvi_mlp_fastfood_apply_bwd_supported(int32_t first, int32_t n_mid, int32_t log2d);
+int64_t whvi_mlp_fastfood_apply_bwd_workspace(int64_t S, int64_t B, int32_t first, int32_t n_mid, int32_t log2d);
+int whvi_mlp_fastfood_apply_bwd_f32(void *grad_w_in, void *grad_s1, void *grad_s2, void *grad_g, void *grad_w_out, void *grad_b,
+                                    void *grad_x, void *work, int64_t work_floats, const void *g, const void *x, int32_t first,
+                                    const void *w_in, const void *b_in, int32_t n_mid, const void *s1, const void *s2,
+                                    const void *gk, const void *b_mid, int32_t mid_bias, const void *w_out, int64_t S, int64_t B,
+                                    int32_t log2d, int32_t act, int32_t act_bits, void *stream);
+
 /* whvi_reparam_kl_f32 with the eps draw inside the kernel: Philox4x32-10 + Box-Muller, one standard
  * normal per (matrix, sample, element), written to eps_out (J, S, D) for the backward pass / inspection.  The
  * generator state is three 64-bit words in DEVICE memory, state = {seed, launch offset, scratch (must be 0)}; the

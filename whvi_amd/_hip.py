@@ -122,6 +122,13 @@ def _declare_f3(lib):
     lib.whvi_mlp_fastfood_apply_f32.restype = ctypes.c_int
     lib.whvi_mlp_fastfood_apply_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32,
                                                 vp]
+    lib.whvi_mlp_fastfood_apply_bwd_supported.restype = ctypes.c_int
+    lib.whvi_mlp_fastfood_apply_bwd_supported.argtypes = [i32, i32, i32]
+    lib.whvi_mlp_fastfood_apply_bwd_workspace.restype = i64
+    lib.whvi_mlp_fastfood_apply_bwd_workspace.argtypes = [i64, i64, i32, i32, i32]
+    lib.whvi_mlp_fastfood_apply_bwd_f32.restype = ctypes.c_int
+    lib.whvi_mlp_fastfood_apply_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp,
+                                                    i32, vp, i64, i64, i32, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -781,6 +788,58 @@ def mlp_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1
             rc = L.whvi_mlp_apply_act_bwd_f32(*args, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply_bwd")
     return grad_w_in, grad_w_mid, grad_w_out, grad_b, grad_x
+
+
+def mlp_fastfood_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_fastfood_apply_bwd_supported`` (include/whvi_hip.h) without the library:
+    ``mlp_fastfood_apply_supported`` with at most 2 square layers and D <= 1024."""
+    return mlp_fastfood_apply_supported(first, n_mid, d) and n_mid <= 2 and d <= 1024
+
+
+def mlp_fastfood_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor,
+                           gk: torch.Tensor, b_mid, w_out: torch.Tensor, *, mid_bias: int = 0, act_bits: int = 0,
+                           need_grad_x: bool = False, act: str = "relu"):
+    """Backward of ``mlp_fastfood_apply`` in one call (whvi_mlp_fastfood_apply_bwd_f32): ``(grad_w_in, grad_s1 (n_mid, D),
+    grad_s2 (n_mid, D), grad_g (n_mid, S, D), grad_w_out (S, D), grad_b ((1 + n_mid) D + 1: b_in, b_mid rows, b_out),
+    grad_x (S, B, K) or None)`` from ``g`` = dL/dy (S, B) and the forward's operands (``gk`` is its ``g``; same shapes,
+    ``act_bits`` and ``act`` as ``mlp_fastfood_apply``)."""
+    code = _mlp_act(act)
+    S, D = w_out.shape
+    n_mid = s1.shape[0]
+    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
+    if not mlp_fastfood_apply_bwd_supported(first, n_mid, D):
+        raise RuntimeError(f"mlp_fastfood_apply_bwd: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
+    B = x.shape[0]
+    ops = (g, x, w_in, s1, s2, gk, w_out) + tuple(t for t in (b_in, b_mid) if t is not None)
+    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
+        raise RuntimeError("mlp_fastfood_apply_bwd: float32 CUDA tensors on one device only")
+    if (tuple(g.shape) != (S, B) or tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D)
+            or tuple(s1.shape) != (n_mid, D) or tuple(s2.shape) != (n_mid, D) or tuple(gk.shape) != (n_mid, S, D)
+            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)):
+        raise RuntimeError("mlp_fastfood_apply_bwd: operand shapes do not match")
+    g, x, w_in, s1, s2, gk, w_out = (_aligned(t) for t in (g, x, w_in, s1, s2, gk, w_out))
+    b_in, b_mid = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid))
+    dev = x.device
+    grad_w_in = torch.empty(tuple(w_in.shape), dtype=torch.float32, device=dev)
+    grad_s1 = torch.empty((n_mid, D), dtype=torch.float32, device=dev)
+    grad_s2 = torch.empty((n_mid, D), dtype=torch.float32, device=dev)
+    grad_g = torch.empty((n_mid, S, D), dtype=torch.float32, device=dev)
+    grad_w_out = torch.empty((S, D), dtype=torch.float32, device=dev)
+    grad_b = torch.empty(((1 + n_mid) * D + 1,), dtype=torch.float32, device=dev)
+    grad_x = torch.empty((S, B, first), dtype=torch.float32, device=dev) if need_grad_x else None
+    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    L = lib()
+    log2d = D.bit_length() - 1
+    with _OnDevice(dev):
+        n = int(L.whvi_mlp_fastfood_apply_bwd_workspace(S, B, first, n_mid, log2d))
+        work = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+        rc = L.whvi_mlp_fastfood_apply_bwd_f32(grad_w_in.data_ptr(), grad_s1.data_ptr(), grad_s2.data_ptr(), grad_g.data_ptr(),
+                                               grad_w_out.data_ptr(), grad_b.data_ptr(), ptr(grad_x), work.data_ptr(), n,
+                                               g.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
+                                               s1.data_ptr(), s2.data_ptr(), gk.data_ptr(), ptr(b_mid), int(mid_bias),
+                                               w_out.data_ptr(), S, B, log2d, code, int(act_bits), _stream(x))
+    _check(rc, "whvi_mlp_fastfood_apply_bwd")
+    return grad_w_in, grad_s1, grad_s2, grad_g, grad_w_out, grad_b, grad_x
 
 
 def reparam_kl_bwd(grad_u, grad_kl, g_mu, g_rho, eps, sigma, lambda_: float):

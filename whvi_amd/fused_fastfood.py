@@ -1,5 +1,6 @@
-"""The one-launch predictive pass of a WHVI regression network whose square layers are fastfood layers (opt-in:
-``WHVINetwork.set_fused_inference()``, the flag of ``whvi_amd.fused_mlp``).
+"""The one-launch passes of a WHVI regression network whose square layers are fastfood layers: the predictive pass (opt-in:
+``WHVINetwork.set_fused_inference()``) and the training pass, forward + backward (opt-in: ``WHVINetwork.set_fused_training()``)
+-- the flags of ``whvi_amd.fused_mlp``.
 
 A fastfood network -- ``[WHVILinear(n_in, D), act, WHVILinear(D, D, mode="fastfood"), act, ..., WHVILinear(D, 1)]`` -- has the
 outer shape of ``fused_mlp``'s networks, but each square layer applies the paper's operator ``s1 * H(g_k * H(s2 * h))``
@@ -11,9 +12,18 @@ reads ``x`` and writes ``y`` only.  Every layer's operands come from the ``_mc_o
 calls, in module order, so the draws are the same; the kernel repeats the arithmetic of the launches it replaces (the fused
 kernel's butterfly network, the bias as its own add), so the result is bit-identical to ``forward_batched`` without the flag.
 
-``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples)`` adds the checks of one call, ``run``
-makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the caller
-then takes the batched route.  There is no backward: a call that wants an autograd graph is refused."""
+Training: ``FastfoodMLPApplyFunction`` wraps the same launch in an autograd Function that saves only its inputs.  Its backward
+is one call of ``whvi_mlp_fastfood_apply_bwd_f32`` (whvi_amd/csrc/mlp_fastfood_apply_bwd.hpp), which recomputes every row's
+hidden vectors with the forward's arithmetic and applies the batched route's backward formulas (``FastfoodFunction.backward``,
+and per boundary the activation backward that route runs there); the batch sums run in a fixed order (bit-identical gradients
+on every run).  They differ from the batched route's gradients only by summation order; the loss is bit-identical.  The
+gradient w.r.t. every sample's ``g_k`` goes back through ``_mc_operands`` to ``g_mu`` and ``g_rho`` by autograd.  There is no
+double backward.
+
+``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples[, training])`` adds the checks of one call,
+``run`` makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the
+caller then takes the batched route.  The predictive plan (``training=False``) refuses a call that wants an autograd graph;
+the training plan (``training=True``) takes exactly those, within ``whvi_mlp_fastfood_apply_bwd_f32``'s narrower range."""
 from typing import List, NamedTuple, Union
 
 import torch
@@ -24,7 +34,7 @@ from whvi_amd.fastfood import WHVIFastfoodMatrix
 from whvi_amd.fused_mlp import _act_bits, _first_layer, _output_layer, _scan
 from whvi_amd.weights import WHVIColumnMatrix, WHVISquarePow2Matrix, WHVIStackedMatrix
 
-__all__ = ["Plan", "match", "plan", "run"]
+__all__ = ["Plan", "FastfoodMLPApplyFunction", "match", "plan", "run"]
 
 
 class Plan(NamedTuple):
@@ -77,9 +87,11 @@ def match(net) -> Union[Plan, str]:
     return Plan(first, kind, n_in, list(mids), last, layers, D, act or "relu", _act_bits(act_after))
 
 
-def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
+def plan(net, x: torch.Tensor, n_samples: int, training: bool = False) -> Union[Plan, str]:
     """``match(net)`` plus the checks of this call: float32 CUDA input and parameters on x's device, sizes, and no autograd
-    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad)."""
+    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad).  ``training=True``: the plan of the
+    trainable pass instead -- the same checks, but a graph must be wanted and the network must lie in the backward's range
+    (``_hip.mlp_fastfood_apply_bwd_supported``)."""
     p = match(net)
     if isinstance(p, str):
         return p
@@ -91,17 +103,54 @@ def plan(net, x: torch.Tensor, n_samples: int) -> Union[Plan, str]:
     S, B = int(n_samples), x.shape[0]
     if S < 1 or S * B >= 2 ** 32:
         return f"{S} samples x {B} rows: outside 1 .. 2^32 - 1 rows"
-    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params)):
-        return "an autograd graph is wanted (the fused fastfood pass has no backward)"
+    wanted = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params))
+    if not training:
+        return "an autograd graph is wanted (the fused fastfood pass has no backward)" if wanted else p
+    if not wanted:
+        return "no autograd graph is wanted (the training pass is for passes that need one)"
+    if not _hip.mlp_fastfood_apply_bwd_supported(p.kind, len(p.mids), p.D):
+        return f"hidden width {p.D} with {len(p.mids)} fastfood layers is outside whvi_mlp_fastfood_apply_bwd's range"
     return p
+
+
+class FastfoodMLPApplyFunction(torch.autograd.Function):
+    """``y (S, B) = mlp_fastfood_apply(x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out)`` (whvi_mlp_fastfood_apply_f32) with a
+    backward: one call of ``whvi_mlp_fastfood_apply_bwd_f32`` that recomputes the hidden vectors instead of reading saved ones
+    (only the inputs are saved).  ``s1, s2`` (n_mid, D), ``g`` (n_mid, S, D): every sample's ``g_k``, whose gradient is returned
+    as is.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out, mid_bias, act_bits, act="relu"):
+        ctx.mid_bias, ctx.act_bits, ctx.act = int(mid_bias), int(act_bits), act
+        ctx.save_for_backward(x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out)
+        return _hip.mlp_fastfood_apply(x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out, mid_bias=mid_bias, act_bits=act_bits,
+                                       act=act)
+
+    @staticmethod
+    def backward(ctx, gy):
+        if torch.is_grad_enabled():
+            raise RuntimeError("FastfoodMLPApplyFunction: the fused training pass has no double backward -- call backward() "
+                               "without create_graph=True, or turn WHVINetwork.set_fused_training off for this pass")
+        x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gw_in, gs1, gs2, gg, gw_out, gb, gx = _hip.mlp_fastfood_apply_bwd(gy, x, w_in, b_in, s1, s2, g, b_mid, w_out,
+                                                                          mid_bias=ctx.mid_bias, act_bits=ctx.act_bits,
+                                                                          need_grad_x=need[0], act=ctx.act)
+        n_mid, S, D = gg.shape
+        grad_x = gx.sum(dim=0) if gx is not None else None
+        grad_b_in = gb[:D].view(b_in.shape) if b_in is not None else None
+        grad_b_mid = gb[D:(1 + n_mid) * D].view(b_mid.shape) if b_mid is not None else None
+        grad_b_out = gb[(1 + n_mid) * D:].view(b_out.shape) if b_out is not None else None
+        return grad_x, gw_in, grad_b_in, gs1, gs2, gg, grad_b_mid, gw_out, grad_b_out, None, None, None
 
 
 def _bias(w):
     return None if w.bias is None else w.bias.reshape(-1)
 
 
-def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
-    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch.
+def run(net, p: Plan, x: torch.Tensor, n_samples: int, training: bool = False) -> torch.Tensor:
+    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch
+    (``training``: through ``FastfoodMLPApplyFunction``, for a plan of ``plan(..., training=True)``).
     Returns ``(batch, 1, S)`` in forward_batched's layout; sets ``net._pass_kl`` as the batched route does -- to None, because
     fastfood layers report no in-pass KL."""
     S = int(n_samples)
@@ -124,7 +173,11 @@ def run(net, p: Plan, x: torch.Tensor, n_samples: int) -> torch.Tensor:
     b_mid = None
     if mid_bias:
         b_mid = torch.stack([w.bias.reshape(-1) if w.bias is not None else torch.zeros_like(w.s1) for w in p.mids])
-    y = _hip.mlp_fastfood_apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias=mid_bias,
-                                act_bits=p.act_bits, act=p.act)
+    if training:
+        y = FastfoodMLPApplyFunction.apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias, p.act_bits,
+                                           p.act)
+    else:
+        y = _hip.mlp_fastfood_apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias=mid_bias,
+                                    act_bits=p.act_bits, act=p.act)
     net._pass_kl = None
     return y.unsqueeze(-1).permute(1, 2, 0)

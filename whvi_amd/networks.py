@@ -99,7 +99,7 @@ class WHVINetwork(nn.Module, WHVI):
         the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before (a pass that wants
         a graph takes the fused route only with ``set_fused_training``).  Networks whose square layers are all fastfood layers
         (``WHVILinear(D, D, mode="fastfood")``, 1 .. 4 of them) take ``whvi_amd.fused_fastfood`` under the same flag and rules
-        (bit for bit for every activation; no trainable form).  ``eval_model`` evaluates under ``torch.no_grad()`` while the
+        (bit for bit for every activation; their trainable form is ``set_fused_training``'s too).  ``eval_model`` evaluates under ``torch.no_grad()`` while the
         flag is on."""
         self.fused_inference = bool(on)
         return self
@@ -111,7 +111,9 @@ class WHVINetwork(nn.Module, WHVI):
         ``set_fused_inference`` covers, with at most 2 square layers and D <= 1024.  A ``forward_batched`` call that wants an
         autograd graph then makes the same draws, returns the forward values ``set_fused_inference`` returns and saves no
         ``(S, batch, D)`` activation; its gradients differ from the batched route's only by summation order, and are the same on
-        every run.  No double backward (``create_graph=True`` raises).  Every other call takes the route it takes without this
+        every run.  Networks whose square layers are all fastfood layers take ``whvi_amd.fused_fastfood``'s trainable pass under
+        the same flag (``whvi_mlp_fastfood_apply_f32`` forward, ``whvi_mlp_fastfood_apply_bwd_f32`` backward; at most 2 fastfood
+        layers, D <= 1024).  No double backward (``create_graph=True`` raises).  Every other call takes the route it takes without this
         flag; the two flags are independent."""
         self.fused_training = bool(on)
         return self
@@ -153,6 +155,10 @@ class WHVINetwork(nn.Module, WHVI):
             plan = fused_mlp.plan(self, x, n_samples, training=True)
             if not isinstance(plan, str):
                 return fused_mlp.run(self, plan, x, n_samples, training=True)
+            from whvi_amd import fused_fastfood          # fastfood square layers (whvi_mlp_fastfood_apply_bwd_f32)
+            plan = fused_fastfood.plan(self, x, n_samples, training=True)
+            if not isinstance(plan, str):
+                return fused_fastfood.run(self, plan, x, n_samples, training=True)
         h = x
         fused_kl, complete = None, True
         modules = list(self.sequential)
