@@ -194,6 +194,28 @@ int whvi_fused_shs_ex_f64(void *dst, const void *src, const void *a, const void 
                           int64_t sample_stride, int64_t group_rows, int32_t axis,
                           int32_t flags, void *stream);
 
+/* The same pipeline on 16-bit ACTIVATION streams: dst / src are IEEE half (_f16) or bfloat16 (_bf16), in place or out of
+ * place; a, b, c are FLOAT32 vectors (they are the layer's float32 parameters; nothing is gained by rounding them).  Each
+ * element is converted to f32 exactly, every multiply is its own f32 rounding, the butterflies are f32 adds / subs in the
+ * reference's stage order, and the result is rounded to the storage type ONCE (round to nearest even; a bf16 NaN stays a
+ * NaN), when the tile is stored: element for element the value of whvi_fused_shs_ex_f32 on the upcast input, cast once --
+ * not the five roundings of the unfused 16-bit chain.  The sign of a zero result is exempt as it is for the f32 entry.
+ * HBM traffic: 2 bytes read + 2 written per element.
+ *   Supported: axis = WHVI_AXIS_COL with src != NULL, 3 <= log2d <= 13 (rows of one 16-byte chunk up to one wavefront tile),
+ *   flags 0, WHVI_FUSED_A_PER_SAMPLE, WHVI_FUSED_C_PER_SAMPLE.  group_rows is checked (>= 1) and otherwise ignored.
+ *   Refused with WHVI_ERR_ARG and a message naming the form: axis = WHVI_AXIS_ROW and src == NULL (the weight construction
+ *   is float32), WHVI_FUSED_SRC_SHARED and WHVI_FUSED_ONE_TRANSFORM (a 16-bit intermediate between the two halves would be a
+ *   second rounding).  log2d outside [3, 13]: WHVI_ERR_SIZE.  Otherwise the argument checks of whvi_fused_shs_ex_f32, and
+ *   dst must not overlap a scale vector (WHVI_ERR_OVERLAP). */
+int whvi_fused_shs_ex_f16 (void *dst, const void *src, const void *a, const void *b,
+                           const void *c, int64_t rows, int32_t log2d, int64_t n_samples,
+                           int64_t sample_stride, int64_t group_rows, int32_t axis,
+                           int32_t flags, void *stream);
+int whvi_fused_shs_ex_bf16(void *dst, const void *src, const void *a, const void *b,
+                           const void *c, int64_t rows, int32_t log2d, int64_t n_samples,
+                           int64_t sample_stride, int64_t group_rows, int32_t axis,
+                           int32_t flags, void *stream);
+
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample
  * (src/weights.py:82-83,92), and kl_diag_normal(g_mu, g_sigma, 0, lambda) (src/weights.py:52-64,

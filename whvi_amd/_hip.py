@@ -59,6 +59,10 @@ def _declare(lib):
         fn = getattr(lib, "whvi_fused_shs_ex_" + sfx)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i64, i64, i32, i32, vp]
+    for sfx in ("f16", "bf16"):                       # 16-bit activations, float32 scale vectors: the _ex form only
+        fn = getattr(lib, "whvi_fused_shs_ex_" + sfx)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, i64, i32, i64, i64, i64, i32, i32, vp]
 
 
 def _declare_f3(lib):
@@ -271,18 +275,24 @@ def stream_copy_probe(src: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
 
 
 FUSED_A_PER_SAMPLE, FUSED_C_PER_SAMPLE, FUSED_SRC_SHARED, FUSED_ONE_TRANSFORM = 1, 2, 4, 8
+_HALF_DTYPES = (torch.float16, torch.bfloat16)
 
 
 def fused_src_shared_supported(dtype: torch.dtype, d: int) -> bool:
     """Row lengths the shared-source form of ``whvi_fused_shs_*`` covers (rows of at least 64 sixteen-byte chunks)."""
+    if dtype not in (torch.float32, torch.float64):
+        return False                                  # 16-bit storage has the two-transform launch on its own rows only
     return fused_supported(dtype, d) and d * (4 if dtype == torch.float32 else 8) >= 1024
 
 
 def fused_supported(dtype: torch.dtype, d: int) -> bool:
-    """Row lengths ``whvi_fused_shs_*`` covers: one wavefront tile, D <= 8192 (f32) / 4096 (f64).  Longer rows have the
-    plain transform only (``fwht_rows``: a block per row, then passes)."""
+    """Row lengths ``whvi_fused_shs_*`` covers: one wavefront tile, D <= 8192 (f32) / 4096 (f64); float16 / bfloat16
+    activations (float32 scale vectors, ``axis="col"`` with a source only) rows of one 16-byte chunk up to one tile,
+    8 <= D <= 8192.  Longer rows have the plain transform only (``fwht_rows``: a block per row, then passes)."""
     if dtype == torch.float32:
         return 1 <= d <= 8192
+    if dtype in _HALF_DTYPES:
+        return 8 <= d <= 8192
     return dtype == torch.float64 and 1 <= d <= 4096
 
 
@@ -297,8 +307,19 @@ def fused_shs(src, a=None, b=None, c=None, *, axis: str = "col", n_samples: int 
     ``src_shared`` (axis="col"): ``src`` is ``(sample_stride, d)`` -- ONE sample's rows, shared by all ``n_samples``
     samples -- and the result has ``n_samples * sample_stride`` rows in (sample, row) order (WHVI_FUSED_SRC_SHARED).
     ``one_transform`` (axis="col", ``c`` must be None): ``out[r] = a (.) FWHT(b_s (.) src[r])``, the second half alone.
+
+    float16 / bfloat16 ``src`` (whvi_fused_shs_ex_f16 / _bf16): ``a``, ``b``, ``c`` are taken as float32, the arithmetic is
+    float32 and the result is rounded to ``src``'s dtype ONCE, when it is stored -- the float32 pipeline on the upcast
+    input, cast once.  ``axis="col"`` with a source only: ``axis="row"``, ``src=None``, ``src_shared`` and ``one_transform``
+    raise.
     """
     ax = {"row": AXIS_ROW, "col": AXIS_COL}[axis]
+    half = (src.dtype if src is not None else dtype) in _HALF_DTYPES
+    if half:
+        for refused, form in ((src is None, "src=None (identity source)"), (ax == AXIS_ROW, "axis='row'"),
+                              (src_shared, "src_shared"), (one_transform, "one_transform")):
+            if refused:
+                raise RuntimeError(f"fused_shs: {form} has no float16 / bfloat16 form (float32 / float64 only)")
     if src is not None:
         if src.device.type != "cuda" or src.dim() != 2:
             raise RuntimeError("fused_shs: src must be a 2-D CUDA tensor")
@@ -309,8 +330,11 @@ def fused_shs(src, a=None, b=None, c=None, *, axis: str = "col", n_samples: int 
             if ax != AXIS_COL or rows != sample_stride or not fused_src_shared_supported(dtype, d):
                 raise RuntimeError("fused_shs: src_shared needs axis='col', src of sample_stride rows and rows of >= 1 KiB")
             rows = n_samples * sample_stride
-    if dtype not in (torch.float32, torch.float64):
-        raise RuntimeError("fused_shs: float32 / float64 only")
+    if half:
+        if not fused_supported(dtype, d):
+            raise RuntimeError(f"fused_shs: {dtype} rows of {d} elements are outside the supported range 8 .. 8192")
+    elif dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("fused_shs: float32 / float64 only (float16 / bfloat16: axis='col' with a source)")
     if d < 1 or (d & (d - 1)) != 0:
         raise RuntimeError("n must be a power of 2")
     log2d = d.bit_length() - 1
@@ -318,7 +342,7 @@ def fused_shs(src, a=None, b=None, c=None, *, axis: str = "col", n_samples: int 
     def prep(v, n):
         if v is None:
             return None
-        v = _aligned(v.to(device=device, dtype=dtype).reshape(-1))
+        v = _aligned(v.to(device=device, dtype=torch.float32 if half else dtype).reshape(-1))
         if v.numel() != n:
             raise RuntimeError(f"fused_shs: scale vector has {v.numel()} elements, expected {n}")
         return v

@@ -3,6 +3,7 @@
 // per-dtype translation units (fwht_<dtype>.hip, fused_<dtype>.hip).  The C ABI itself is
 // declared in include/whvi_hip.h.
 #include "kernels.hpp"
+#include "fused16.hpp"
 
 namespace whvi {
 
@@ -669,6 +670,115 @@ inline int fused_dispatch(void *dst, const void *src, const void *a, const void 
     }
 #undef WHVI_CASE
     return after_launch("fused_shs");
+}
+
+// ---- fused pipeline, 16-bit activation storage with float32 scale vectors (fused16.hpp) ------------------------------
+template <typename T, int LOG2D>
+inline void launch_fused16(void *dst, const void *src, const float *a, const float *b, const float *c, int64_t rows,
+                           int64_t n_samples, int64_t sample_stride, int flags, hipStream_t st)
+{
+    constexpr int K = pick_k<T, LOG2D>();
+    constexpr int VEC = Elem<T>::VEC;
+    constexpr bool SMALL_TILE = tile_vgprs<T, K>() <= 64;
+    const int64_t n_chunks = (rows << LOG2D) / VEC;
+    const int64_t n_tiles = (n_chunks + 64 * K - 1) / (64 * K);
+    const FastDiv ds = make_fastdiv((uint32_t)sample_stride), dn = make_fastdiv((uint32_t)n_samples);
+    const bool big = n_tiles >= (int64_t)(SMALL_TILE ? 32 : 16) * num_cu();
+    const bool nt = big && stream_sized(n_chunks * 16, dst, src);
+#define WHVI_FUSED16(NT, STG)                                                                                   \
+    do {                                                                                                        \
+        constexpr size_t smem = ((STG) == STAGE_ABC ? 3 : ((STG) == STAGE_AC ? 2 : 0)) * sizeof(float) << LOG2D; \
+        note_launch<T>("fused_shs16_kernel", LOG2D, K, (bool)NT, (int)POLICY_DPP, (int)STG, 256);               \
+        hipLaunchKernelGGL((fused_shs16_kernel<T, LOG2D, K, NT, POLICY_DPP, STG, 256>), dim3((unsigned)((n_tiles + 3) / 4)), \
+                           dim3(256), smem, st, (u32x4 *)dst, (const u32x4 *)src, a, b, c, n_chunks, n_tiles, ds, dn, flags); \
+    } while (0)
+    // Which vectors a block stages in LDS (as float32), for launches that fill the chip and rows of >= 64 chunks (D >= 512):
+    //   * every row of a block in ONE sample (one sample in all, or rows in (sample, batch, D) order with sample_stride a
+    //     multiple of the rows per block): that sample's a, b and c -- no scale vector comes through L2 -> L1 at all.  Here b
+    //     is worth staging, unlike in the f32 kernel: per 16-byte chunk of data a vector is 32 bytes, so three L2-sourced
+    //     vectors are six loads per tile load.  D = 8192 stages a and c only (three vectors would be 96 KiB of LDS);
+    //   * otherwise shared a / c are staged and per-sample ones come from L2.
+    if constexpr (LOG2D >= 9) {
+        constexpr int64_t rows_per_block = ((int64_t)4 * 64 * K * VEC) >> LOG2D;
+        const bool one_sample_blocks = n_samples == 1 || sample_stride % rows_per_block == 0;
+        const bool shared_ac = (flags & (WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE)) == 0;
+        if (big && one_sample_blocks && LOG2D <= 12) {
+            if constexpr (LOG2D <= 12) { if (nt) WHVI_FUSED16(true, STAGE_ABC); else WHVI_FUSED16(false, STAGE_ABC); }
+            return;
+        }
+        if (big && (one_sample_blocks || shared_ac)) {
+            if (nt) WHVI_FUSED16(true, STAGE_AC); else WHVI_FUSED16(false, STAGE_AC);
+            return;
+        }
+    }
+    if (nt) WHVI_FUSED16(true, STAGE_NONE);
+    else WHVI_FUSED16(false, STAGE_NONE);
+#undef WHVI_FUSED16
+}
+
+inline bool ranges_overlap(const void *p, int64_t pbytes, const void *q, int64_t qbytes)
+{
+    const char *x = (const char *)p, *y = (const char *)q;
+    return q != nullptr && x < y + qbytes && y < x + pbytes;
+}
+
+// Argument checks of the f32 entry (null, alignment, overlap, sizes, log2d range) plus the forms that have no 16-bit
+// kernel: the row axis, the identity source, the shared source and the one-transform half (include/whvi_hip.h).
+template <typename T>
+inline int fused16_dispatch(void *dst, const void *src, const void *a, const void *b, const void *c,
+                            int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride,
+                            int64_t group_rows, int32_t axis, int32_t flags, void *stream)
+{
+    static_assert(sizeof(T) == 2, "16-bit storage");
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    g_err[0] = 0;
+    if (axis != WHVI_AXIS_ROW && axis != WHVI_AXIS_COL)
+        return fail(WHVI_ERR_ARG, "whvi: bad axis%s %lld", "", axis);
+    if (flags & ~(WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE | WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM))
+        return fail(WHVI_ERR_ARG, "whvi: unknown fused flags%s 0x%llx", "", flags);
+    if (axis == WHVI_AXIS_ROW)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no row-axis form%s: its weight "
+                    "construction is float32", "");
+    if (flags & WHVI_FUSED_SRC_SHARED)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no shared-source form%s: the input is expanded by the caller", "");
+    if (flags & WHVI_FUSED_ONE_TRANSFORM)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no one-transform form%s: a "
+                    "16-bit intermediate would be a second rounding", "");
+    if (src == nullptr && dst != nullptr && rows > 0)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no identity-source form (src == NULL)%s", "");
+    if (log2d >= 0 && log2d < LV)
+        return fail(WHVI_ERR_SIZE, "whvi: log2(D)%s = %lld is outside the supported range [3, %lld] of the 16-bit fused pipeline",
+                    "", log2d, max_single_pass_log2d<T>());
+    int rc = check_common(dst, src, rows, log2d, max_single_pass_log2d<T>(), sizeof(T));
+    if (rc != WHVI_OK) return rc;
+    if (n_samples < 1 || sample_stride < 1 || group_rows < 1)
+        return fail(WHVI_ERR_ARG, "whvi: n_samples, sample_stride and group_rows must be >= 1%s", "");
+    if (rows >= ((int64_t)1 << 32) || n_samples >= ((int64_t)1 << 32) || sample_stride >= ((int64_t)1 << 32) ||
+        group_rows >= ((int64_t)1 << 32))
+        return fail(WHVI_ERR_SIZE, "whvi: the fused pipeline indexes rows with 32 bits%s", "");
+    if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15))
+        return fail(WHVI_ERR_ALIGN, "whvi: column scale vectors must be 16-byte aligned%s", "");
+    if (rows == 0) return WHVI_OK;
+    {
+        const int64_t dbytes = (rows << log2d) * (int64_t)sizeof(T), vbytes = (int64_t)sizeof(float) << log2d;
+        if (ranges_overlap(dst, dbytes, a, vbytes * ((flags & WHVI_FUSED_A_PER_SAMPLE) ? n_samples : 1)) ||
+            ranges_overlap(dst, dbytes, b, vbytes * n_samples) ||
+            ranges_overlap(dst, dbytes, c, vbytes * ((flags & WHVI_FUSED_C_PER_SAMPLE) ? n_samples : 1)))
+            return fail(WHVI_ERR_OVERLAP, "whvi: dst overlaps a scale vector%s", "");
+    }
+    hipStream_t st = (hipStream_t)stream;
+#define WHVI_CASE(L)                                                                                                \
+    case L:                                                                                                         \
+        launch_fused16<T, L>(dst, src, (const float *)a, (const float *)b, (const float *)c, rows, n_samples,       \
+                             sample_stride, flags, st);                                                             \
+        break;
+    switch (log2d) {
+        WHVI_CASE(3) WHVI_CASE(4) WHVI_CASE(5) WHVI_CASE(6) WHVI_CASE(7) WHVI_CASE(8) WHVI_CASE(9) WHVI_CASE(10)
+        WHVI_CASE(11) WHVI_CASE(12) WHVI_CASE(13)
+    default: break;
+    }
+#undef WHVI_CASE
+    return after_launch("fused_shs (16-bit)");
 }
 
 }  // namespace whvi

@@ -15,6 +15,11 @@ initialisation and KL as `WHVISquarePow2Matrix` (src/weights.py:28-32, :52-64), 
 Parity: bit-exact against `oracle.pipeline(axis="col")` (compositions of the reference's own primitives --
 `matmul_diag_right`, src/utils.py:15-23, and the C++ FWHT) and against the dense product with `build_H` in float64
 (tests/test_fastfood.py).  Host tensors run the same ops through the host FWHT.
+
+16-bit activations (opt-in, ``WHVIFastfoodMatrix.keep_half``): a float16 / bfloat16 CUDA input is by default promoted to
+float32 by the first multiply and comes back as float32 through separate launches.  With ``keep_half = True`` the forward is
+ONE launch of ``whvi_fused_shs_ex_f16 / _bf16`` -- float32 parameters, float32 arithmetic, one rounding when the row is
+stored, 2 bytes read + 2 written per element -- and returns the input's dtype.
 """
 import torch
 import torch.nn as nn
@@ -35,10 +40,14 @@ def _fwht(x):
     return fwht_cpp.forward(x)
 
 
-def _pipeline(x, a, b, c, n_samples, sample_stride, shared=False):
+_HALF = (torch.float16, torch.bfloat16)
+
+
+def _pipeline(x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False):
     """a * fwht(b[s(r)] * fwht(c * x[r])) for every row r, s(r) = (r // sample_stride) % n_samples.  ``shared``: ``x`` holds
     ONE sample's rows (``sample_stride`` of them) and every sample reads them -- on the GPU straight from the caches
-    (WHVI_FUSED_SRC_SHARED), elsewhere after expanding."""
+    (WHVI_FUSED_SRC_SHARED), elsewhere after expanding.  16-bit ``x`` takes the fused launch only with ``keep_half``
+    (it has no shared-source form: the input is expanded); without it, it is promoted to float32 by ``c * x`` below."""
     if shared:
         if x.device.type == "cuda":
             from whvi_amd import _hip
@@ -51,7 +60,7 @@ def _pipeline(x, a, b, c, n_samples, sample_stride, shared=False):
         x = x.repeat(n_samples, 1)
     if x.device.type == "cuda":
         from whvi_amd import _hip
-        if _hip.fused_supported(x.dtype, x.size(1)):
+        if _hip.fused_supported(x.dtype, x.size(1)) and (keep_half or x.dtype not in _HALF):
             return _hip.fused_shs(x, a, b, c, axis="col", n_samples=n_samples, sample_stride=sample_stride)
         # rows longer than one wavefront tile (D > 8192; f64 > 4096): the fused launch does not exist, the plain
         # transform does (a block per row and beyond) -- the same multiplies and butterflies as separate launches
@@ -80,15 +89,22 @@ class FastfoodFunction(torch.autograd.Function):
 
     Forward: one fused launch.  The operator is linear in x and H is symmetric, so the gradient with respect to x is
     the same launch with a and c exchanged; the gradients of the three diagonals are products with the two
-    intermediate transforms (recomputed, not stored) summed over rows.  First order only."""
+    intermediate transforms (recomputed, not stored) summed over rows.  First order only.
+
+    ``keep_half`` (16-bit CUDA ``x`` that ``_hip.fused_supported`` covers, float32 ``a, b, c``): the forward is one 16-bit
+    launch and returns ``x.dtype``; so is a backward that wants ``grad_x`` alone (``a`` and ``c`` exchanged).  A backward that
+    wants a parameter gradient upcasts ``x`` and ``grad_y`` to float32 once -- 2 bytes read + 4 written per element each, and
+    every pass behind them moves 4-byte elements -- runs the float32 code below, and returns float32 parameter gradients
+    and ``grad_x`` cast to ``x.dtype``."""
 
     @staticmethod
-    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False):
+    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False):
         """``shared``: ``x`` is ``(sample_stride, D)``, the same rows for every sample (a layer's first Monte-Carlo pass on
         a ``(batch, D)`` input); the result still has ``n_samples * sample_stride`` rows."""
         ctx.save_for_backward(x, a, b, c)
         ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
-        return _pipeline(x, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared)
+        ctx.keep_half = bool(keep_half) and x.device.type == "cuda" and x.dtype in _HALF
+        return _pipeline(x, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half)
 
     @staticmethod
     @once_differentiable
@@ -98,6 +114,11 @@ class FastfoodFunction(torch.autograd.Function):
         grad_y = grad_y.contiguous()
         need_x, need_a, need_b, need_c = ctx.needs_input_grad[:4]
         grad_x = grad_a = grad_b = grad_c = None
+        x_dtype = x.dtype
+        if ctx.keep_half:
+            if need_x and not (need_a or need_b or need_c or ctx.shared):
+                return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None, None, None, None, None
+            x, grad_y = x.float(), grad_y.float()
         if ctx.shared:
             # every sample read the same rows: their gradients add up (what autograd does for an expanded input)
             fold = lambda g: None if g is None else g.view(S, stride, -1).sum(dim=0)   # noqa: E731
@@ -105,7 +126,7 @@ class FastfoodFunction(torch.autograd.Function):
         else:
             fold = lambda g: g                                                        # noqa: E731
         if need_x and not (need_a or need_b or need_c):
-            return fold(_pipeline(grad_y, c, b, a, S, stride)), None, None, None, None, None, None
+            return fold(_pipeline(grad_y, c, b, a, S, stride)).to(x_dtype), None, None, None, None, None, None, None
         # Every transform of the backward pass is "scale, then FWHT" (optionally scaled again): ONE launch each through the
         # one-transform form of the fused kernel where it exists, the multiply + plain transform elsewhere -- the same
         # roundings either way (tests/test_streaming_parity_gpu.py pins the launch to multiply + fwht_rows bit for bit)
@@ -125,14 +146,15 @@ class FastfoodFunction(torch.autograd.Function):
             if need_c:
                 grad_c = (w * x).sum(dim=0)
             if need_x:
-                grad_x = fold(c * w)
-        return grad_x, grad_a, grad_b, grad_c, None, None, None
+                grad_x = fold(c * w).to(x_dtype)
+        return grad_x, grad_a, grad_b, grad_c, None, None, None, None
 
 
 class WHVIFastfoodMatrix(nn.Module):
     """Square (D, D) WHVI layer in fastfood mode (see the module docstring): parameters ``s1, s2, g_mu, g_rho``
     (+ optional ``bias``) as in ``WHVISquarePow2Matrix``; ``forward(x)`` draws one eps, ``forward_mc(x, S)`` draws S
     and runs all samples in one launch."""
+    keep_half = False         # float16 / bfloat16 CUDA activations: True = one 16-bit launch, output in the input's dtype (False: promoted to float32)
 
     def __init__(self, D, lambda_=1e-5, bias=False):
         super().__init__()
@@ -172,16 +194,22 @@ class WHVIFastfoodMatrix(nn.Module):
         """(batch, D) or (n_samples, batch, D) -> (n_samples, batch, D); sample k uses row k of one
         ``randn(n_samples, D)`` draw."""
         g = self._mc_operands(n_samples)                                          # (S, D)
+        half = False
+        if self.keep_half and x.device.type == "cuda" and x.dtype in _HALF and self.s1.dtype == torch.float32:
+            from whvi_amd import _hip
+            half = _hip.fused_supported(x.dtype, self.D)
+        # (the bias is added in the activation's dtype)
+        bias = None if self.bias is None else (self.bias.to(x.dtype) if half else self.bias)
         if x.dim() == 2:
             # a (batch, D) input shared by all samples: read by every sample straight from the caches, never expanded
             batch = x.size(0)
-            out = FastfoodFunction.apply(x.contiguous(), self.s1, g, self.s2, n_samples, batch, True)
+            out = FastfoodFunction.apply(x.contiguous(), self.s1, g, self.s2, n_samples, batch, True, half)
             out = out.view(n_samples, batch, self.D)
-            return out + self.bias if self.bias is not None else out
+            return out + bias if bias is not None else out
         batch = x.size(1)
         rows = x.reshape(n_samples * batch, self.D).contiguous()
-        out = FastfoodFunction.apply(rows, self.s1, g, self.s2, n_samples, batch).view(n_samples, batch, self.D)
-        return out + self.bias if self.bias is not None else out
+        out = FastfoodFunction.apply(rows, self.s1, g, self.s2, n_samples, batch, False, half).view(n_samples, batch, self.D)
+        return out + bias if bias is not None else out
 
     def forward(self, x):
         out = self.forward_mc(x.reshape(-1, self.D), 1)[0].reshape(x.shape)
