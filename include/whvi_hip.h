@@ -319,6 +319,21 @@ int whvi_diag_apply_f32(void *out, const void *x, const void *s1, const void *s2
                         int64_t S, int64_t B, int32_t log2d, int32_t flags, void *stream);
 int whvi_diag_apply_f64(void *out, const void *x, const void *s1, const void *s2, const void *u, const void *bias,
                         int64_t S, int64_t B, int32_t log2d, int32_t flags, void *stream);
+/* The order in which the launch of whvi_diag_apply_<dtype>(S, B, log2d, flags) -- with out == x when in_place is non-zero --
+ * walks its tiles.  The values are the same in every order; the order decides which XCD's L2 sees which tile, and a test
+ * needs it to know which block map of the kernel a launch exercised (whvi_last_kernel names the instantiation only: the
+ * order also depends on the grid).  Computed by the function the launch itself uses; launches nothing, needs no device.
+ *   WHVI_DIAG_ORDER_PLAIN          block b takes tile group b
+ *   WHVI_DIAG_ORDER_XCD            streaming launch, grid a multiple of 8: the blocks of one XCD walk a contiguous eighth
+ *   WHVI_DIAG_ORDER_SAMPLE_FASTEST streaming launch on a shared input with S > 1, every sample a whole number of 8-block
+ *                                  groups, no WHVI_DIAG_TUNE_PLAIN_ORDER: an XCD runs each of its row groups for all samples
+ *                                  back to back (the input tile is fetched into that XCD's L2 once)
+ * Negative: the error code whvi_diag_apply returns for these arguments before it launches (unknown dtype or flags, log2d
+ * out of range, 2^32 rows or more, a shared input in place).  S * B == 0 (nothing is launched) reports the plain order. */
+#define WHVI_DIAG_ORDER_PLAIN          0
+#define WHVI_DIAG_ORDER_XCD            1
+#define WHVI_DIAG_ORDER_SAMPLE_FASTEST 2
+int32_t whvi_diag_apply_order(int32_t dtype, int64_t S, int64_t B, int32_t log2d, int32_t flags, int32_t in_place);
 
 /* Backward of whvi_diag_apply (closed form; replaces autograd over the GEMM, the weight construction and its op chain):
  *   grad_x : (S, B, D) = g[k, b, :] (.) w_k, or NULL when the input needs no gradient (with WHVI_DIAG_X_SHARED the caller

@@ -6,6 +6,9 @@ through the C butterfly oracle, their sum, a dense product), (b) this library's 
 rocBLAS GEMM) on every shape class of the dispatch, VALUE-identical (`==`, i.e. zeros compare by value: include/whvi_hip.h),
 (c) the same route on NON-FINITE inputs -- inf / NaN in the activations, non-finite and overflowing parameters -- where the
 matrix route turns other outputs into NaN, and (d) its backward against the matrix route's autograd and float64 gradcheck."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
@@ -13,6 +16,9 @@ import torch
 from oracle import whvi_oracle as wo
 from whvi_amd import _hip
 from whvi_amd.weights import DiagApplyFunction, WBarFunction, WHVISquarePow2Matrix
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import kernel_table as kt  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -33,6 +39,11 @@ def matrix_route(x, s1, s2, u, bias, mean_plus=True):
     W = WBarFunction.apply(s1.unsqueeze(0), u.unsqueeze(0), s2.unsqueeze(0), None, mean_plus).squeeze(0)    # (S, D, D)
     out = torch.matmul(x, W.transpose(1, 2))
     return out + bias if bias is not None else out
+
+
+def launch_order(dtype, D, S, B, shared, tune=0, in_place=False):
+    """The block order (whvi_diag_apply_order) of the launch _hip.diag_apply makes for this shape."""
+    return _hip.diag_apply_order(dtype, S, B, D, (_hip.DIAG_X_SHARED if shared else 0) | _hip.DIAG_MEAN_PLUS | tune, in_place)
 
 
 def same_values(a, b):
@@ -94,23 +105,40 @@ def test_value_identical_to_the_matrix_route(dtype, D, S, B, shared, hip_lib):
     # direct weight sampling (src/weights.py:104-108): one w_bar per sample, no mean row
     assert torch.equal(_hip.diag_apply(x, s1, s2, u[1:], bias, n_samples=S, mean_plus=False),
                        matrix_route(x, s1, s2, u[1:], bias, mean_plus=False))
-    # the launch forms a size-based dispatch would not pick here: streaming, and the 16 KiB tiles of streams at a cached size
+    assert launch_order(dtype, D, S, B, shared) == _hip.DIAG_ORDER_PLAIN        # cache-resident: never reordered
+    # the launch forms a size-based dispatch would not pick here: streaming, and the 16 KiB tiles of streams at a cached size;
+    # each in the order the dispatch mirror (tools/kernel_table.py) gives it
+    tname = "float" if dtype == torch.float32 else "double"
     for tune in (_hip.DIAG_TUNE_NT, _hip.DIAG_TUNE_CACHED | 128, _hip.DIAG_TUNE_NT | _hip.DIAG_TUNE_PLAIN_ORDER):
         assert torch.equal(_hip.diag_apply(x, s1, s2, u, bias, n_samples=S, tune=tune), want), tune
-    if not shared:                                                               # in place
+        mirror = kt.diag_apply(tname, S, B, D.bit_length() - 1, (kt.DIAG_X_SHARED if shared else 0) | tune)
+        assert _hip.last_kernel() == mirror.symbol and launch_order(dtype, D, S, B, shared, tune) == mirror.order, (tune, mirror)
+        if not tune & _hip.DIAG_TUNE_NT:
+            assert mirror.order == _hip.DIAG_ORDER_PLAIN                        # a cached launch is never reordered
+    if (D, S, B) == (512, 32, 64):                                               # the one shape here whose NT grid (64 blocks) is reordered
+        assert launch_order(dtype, D, S, B, shared, _hip.DIAG_TUNE_NT) == _hip.DIAG_ORDER_XCD
+    else:
+        assert launch_order(dtype, D, S, B, shared, _hip.DIAG_TUNE_NT) == _hip.DIAG_ORDER_PLAIN
+    if not shared:                                                               # in place, by size and streaming
         assert torch.equal(_hip.diag_apply(x, s1, s2, u, bias, n_samples=S, out=x), want)
+        x.copy_(keep)
+        assert torch.equal(_hip.diag_apply(x, s1, s2, u, bias, n_samples=S, out=x, tune=_hip.DIAG_TUNE_NT), want)
+        assert _hip.last_kernel().endswith(", true, false>")
 
 
 @pytest.mark.parametrize("dtype,D,S,B", [(torch.float32, 512, 32, 4096 + 3), (torch.float32, 1024, 5, 16384 + 1)])
 def test_streaming_size_vs_the_matrix_route_on_sampled_rows(dtype, D, S, B, hip_lib):
-    """> 256 MiB written (the non-temporal launch, XCD-contiguous block order): BASELINE config 2's shape with a ragged
-    batch, shared and per-sample input; sampled rows against the dense product with the sample's matrix."""
+    """> 256 MiB written: the non-temporal launch in the PLAIN block order -- the ragged batches give grids of 4099 and 5121
+    blocks, no multiple of 8, and samples that are no whole number of 8-block groups (the reordered launches are
+    tests/test_diag_apply_orders_gpu.py's).  BASELINE config 2's shape with a ragged batch, shared and per-sample input;
+    sampled rows against the dense product with the sample's matrix."""
     s1, s2, u, bias, g = _operands(dtype, D, S, D + S)
     for shared in (True, False):
         x = torch.randn((B, D) if shared else (S, B, D), device=DEV, dtype=dtype, generator=g)
         got = _hip.diag_apply(x, s1, s2, u, bias, n_samples=S)
         assert got.numel() * got.element_size() > (256 << 20)
         assert _hip.last_kernel().endswith(f", true, {'true' if shared else 'false'}>"), _hip.last_kernel()
+        assert launch_order(dtype, D, S, B, shared) == _hip.DIAG_ORDER_PLAIN
         rng = np.random.default_rng(B)
         bs = torch.from_numpy(np.unique(np.concatenate([[0, 1, 31, 32, B - 2, B - 1], rng.integers(0, B, 40)]))).to(DEV)
         W = WBarFunction.apply(s1.unsqueeze(0), u.unsqueeze(0), s2.unsqueeze(0), None, True).squeeze(0)

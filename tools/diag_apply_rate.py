@@ -1,7 +1,9 @@
 """tools/diag_apply_rate.py -- HIP-event rates of whvi_diag_apply / whvi_diag_apply_bwd against the matrix route
 (weight construction + GEMM) on the layer shapes of BASELINE configs 2 and 4.  GB/s = algorithmic bytes (x read unless shared,
 out written; backward: g + x read, grad_x written) / time."""
-import sys; sys.path.insert(0, "/root/repo")
+import os
+import sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from whvi_amd import _hip
 from whvi_amd.weights import WBarFunction
@@ -32,13 +34,17 @@ for D, S, B, shared in shapes:
     out = torch.empty(S, B, D, device=dev)
     ms = timed(lambda: _hip.diag_apply(x, s1, s2, u, bias, n_samples=S, out=out))
     k = _hip.last_kernel()
+    default = out.clone()
     nbytes = out.numel() * 4 + (0 if shared else x.numel() * 4)
     line = f"D={D} S={S} B={B} shared={int(shared)}: fwd {ms*1e3:8.1f} us {nbytes/ms/1e6:7.0f} GB/s"
     for name, tune in (("nt", 16), ("cached", 32), ("cached big tiles", 32 | 128), ("nt+plain", 16 | 64), ("cached+plain", 32 | 64)):
         if not shared and "plain" in name:
             continue
+        # a variant that computes something else has no rate worth printing
+        assert torch.equal(_hip.diag_apply(x, s1, s2, u, bias, n_samples=S, out=out.fill_(float("nan")), tune=tune), default), name
         ms = timed(lambda: _hip.diag_apply(x, s1, s2, u, bias, n_samples=S, out=out, tune=tune))
         line += f" [{name} {ms*1e3:.1f}]"
+    del default
     gout = torch.randn(S, B, D, device=dev, generator=g)
     for need in (True, False):
         ms = timed(lambda: _hip.diag_apply_bwd(gout, x, s1, s2, u, n_samples=S, need_grad_x=need))

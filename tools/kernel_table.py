@@ -6,9 +6,13 @@ The dispatch (whvi_amd/csrc/layer_apply.hpp, diag_apply.hpp, mlp_apply.hpp, mlp_
 streamed bytes, by tile geometry and by tuning flags; the block order of the non-temporal (NT) launches also depends on the
 grid, and so on the CU count.  The mirrors below restate those rules in Python: each takes shape, flags and CU count and
 returns the demangled symbol ``whvi_last_kernel`` reports, every symbol the call launches (finishing kernels included), the
-grid and whether the XCD-contiguous block order is on.  tests/test_kernel_table_host.py checks that ``CASES`` reaches
-exactly the shipped set of each family; tests/test_kernel_table_gpu.py runs every case against float64 and checks the
-mirror against ``whvi_last_kernel``.  Pure Python: no torch, no GPU.
+grid, whether the XCD-contiguous block order is on and, for diag_apply's forward, the block order as
+whvi_diag_apply_order names it.  tests/test_kernel_table_host.py checks that ``CASES`` reaches exactly the shipped set of
+each family; tests/test_kernel_table_gpu.py runs every case against float64 and checks the mirror against
+``whvi_last_kernel``.  Pure Python: no torch, no GPU.
+
+``ORDER_CASES`` are the launches of diag_apply's forward that tests/test_diag_apply_orders_gpu.py runs: each names the block
+order (plain, XCD-contiguous, sample-fastest within an XCD) it must take.
 
     python tools/kernel_table.py [--cus N]        # every case with its symbol, grid and block order"""
 import sys
@@ -23,8 +27,11 @@ MLP_MAX_LDS = 64 * 1024
 FAMILIES = ("small_k_apply_kernel", "row_dot_kernel", "diag_apply_kernel", "diag_apply_bwd_kernel",
             "diag_apply_bwd_finish_kernel", "mlp_apply_kernel", "mlp_apply_bwd_kernel", "mlp_apply_bwd_finish_kernel")
 
-# symbol: what whvi_last_kernel reports; symbols: every kernel the call launches; xcd: XCD-contiguous block order
-Launch = namedtuple("Launch", "symbol symbols grid nt xcd")
+# symbol: what whvi_last_kernel reports; symbols: every kernel the call launches; xcd: XCD-contiguous block order;
+# order: diag_apply's forward only -- ORDER_PLAIN / ORDER_XCD / ORDER_SAMPLE_FASTEST, the values of whvi_diag_apply_order
+Launch = namedtuple("Launch", "symbol symbols grid nt xcd order", defaults=(None,))
+ORDER_PLAIN, ORDER_XCD, ORDER_SAMPLE_FASTEST = 0, 1, 2
+ORDER_NAMES = ("plain", "xcd", "sample-fastest")
 
 _SIZE = {"float": 4, "double": 8}
 
@@ -92,9 +99,12 @@ def diag_max_log2d(dtype):
     return 12 if dtype == "float" else 11
 
 
-def diag_apply(dtype, S, B, log2d, flags):
-    """diag_apply_dispatch (out of place): NT by TUNE_NT / TUNE_CACHED or by the bytes streamed (x counted unless shared);
-    at cache-resident sizes quarter-size tiles (K = 4) for rows of up to four of their chunks, unless TUNE_BIG_TILES."""
+def diag_apply(dtype, S, B, log2d, flags, in_place=False):
+    """diag_apply_launch (diag_apply.hpp): NT by TUNE_NT / TUNE_CACHED or by the bytes streamed (x counted unless it is
+    shared or the launch is in place); at cache-resident sizes quarter-size tiles (K = 4) for rows of up to four of their
+    chunks, unless TUNE_BIG_TILES.  Block order: sample-fastest within an XCD for a shared input on an NT launch with S > 1,
+    no TUNE_PLAIN_ORDER and every sample a whole number of 8-block groups; else XCD-contiguous for an NT grid that is a
+    multiple of 8; else plain."""
     size = _SIZE[dtype]
     lv = _ilog2(16 // size)
     if not lv <= log2d <= diag_max_log2d(dtype):
@@ -107,14 +117,19 @@ def diag_apply(dtype, S, B, log2d, flags):
     elif flags & DIAG_TUNE_CACHED:
         nt = False
     else:
-        nt = (nbytes if shared else 2 * nbytes) > NT_MIN_BYTES
+        nt = (nbytes if shared or in_place else 2 * nbytes) > NT_MIN_BYTES
     k = pick_k(dtype, log2d)
     need = 1 << (log2d - lv - 6) if log2d > lv + 6 else 1
     if need <= 4 < k and not nt and not flags & DIAG_TUNE_BIG_TILES:
         k = 4
     grid = _cdiv(_cdiv((rows << log2d) * size // 16, 64 * k), 4)
     sym = f"whvi::diag_apply_kernel<{dtype}, {log2d}, {k}, {_b(nt)}, {_b(shared)}>"
-    return Launch(sym, (sym,), grid, nt, nt and grid % 8 == 0)
+    blk_chunks, per_sample = 4 * 64 * k, (B << log2d) * size // 16
+    if shared and nt and S > 1 and not flags & DIAG_TUNE_PLAIN_ORDER and per_sample % (8 * blk_chunks) == 0:
+        order = ORDER_SAMPLE_FASTEST
+    else:
+        order = ORDER_XCD if nt and grid % 8 == 0 else ORDER_PLAIN
+    return Launch(sym, (sym,), grid, nt, order == ORDER_XCD, order)
 
 
 def diag_apply_bwd_slabs(dtype, S, B, log2d, cus):
@@ -240,6 +255,47 @@ def _diag_cases():
     return fwd, bwd
 
 
+def _order_cases():
+    """diag_apply's forward on each of its three block orders (tests/test_diag_apply_orders_gpu.py).  "order" is the order
+    the launch must take; "grid" the grid the comments of that suite quote.  Options are spread so that bias on / off, no
+    mean row, relu_in and relu_out each occur under each order."""
+    P, X, F = ORDER_PLAIN, ORDER_XCD, ORDER_SAMPLE_FASTEST
+    NT = DIAG_TUNE_NT
+    rows = [
+        # id, dtype, log2d, S, B, shared, tune, order, grid, mean_plus, bias, relu_in, relu_out
+        # ---- forced with DIAG_TUNE_NT, a few MiB each
+        ("nt_L10_S3_one_group", "float", 10, 3, 128, True, NT, F, 24, True, True, False, False),      # one group per sample, odd S
+        ("nt_L10_S7", "float", 10, 7, 128, True, NT, F, 56, False, False, True, False),
+        ("nt_L12_S5_three_groups", "float", 12, 5, 96, True, NT, F, 120, True, True, False, True),
+        ("nt_L9_S3", "float", 9, 3, 768, True, NT, F, 72, True, False, True, True),
+        ("nt_L2_S2_shortest_rows", "float", 2, 2, 32768, True, NT, F, 16, False, True, False, False),
+        ("nt_f64_L11_S5", "double", 11, 5, 64, True, NT, F, 80, True, True, True, False),
+        ("nt_L10_S3_plain_order_flag", "float", 10, 3, 128, True, NT | DIAG_TUNE_PLAIN_ORDER, X, 24, False, True, False, True),
+        ("nt_L10_S1_guard", "float", 10, 1, 128, True, NT, X, 8, True, False, True, False),              # the S > 1 guard
+        ("nt_L10_S8_straddling", "float", 10, 8, 129, True, NT, P, 65, False, False, True, True),        # blocks straddle samples
+        ("nt_L10_S3_per_sample", "float", 10, 3, 128, False, NT, X, 24, True, True, False, False),
+        ("nt_L10_S3_per_sample_odd", "float", 10, 3, 130, False, NT, P, 25, True, True, False, False),
+        # ---- dispatched by size (no tuning flag): 512 MiB .. 4 GiB written
+        ("size_L10_S16_B8192", "float", 10, 16, 8192, True, 0, F, 8192, True, True, False, True),        # tools/diag_apply_rate.py
+        ("size_L9_S32_B8192", "float", 9, 32, 8192, True, 0, F, 8192, True, False, True, False),         # config 2's width
+        ("size_L11_S64_B8192", "float", 11, 64, 8192, True, 0, F, 65536, True, True, False, False),      # the bench's module leg
+        ("size_f64_L11_S3_B16384", "double", 11, 3, 16384, True, 0, F, 12288, False, True, True, True),
+        ("size_L10_S16_B8200", "float", 10, 16, 8200, True, 0, X, 8200, True, True, True, True),         # boundaries off samples
+        ("size_L10_S16_B8192_per_sample", "float", 10, 16, 8192, False, 0, X, 8192, True, False, False, True),
+    ]
+    keys = ("id", "dtype", "log2d", "S", "B", "shared", "tune", "order", "grid", "mean_plus", "bias", "relu_in", "relu_out")
+    out = []
+    for r in rows:
+        c = dict(zip(keys, r), family="diag_apply", poison=5)
+        c["id"] = "order_" + c["id"]
+        c["in_place_too"] = c["id"] == "order_size_L10_S16_B8192_per_sample"
+        out.append(c)
+    return out
+
+
+ORDER_CASES = _order_cases()
+
+
 def _mlp_cases():
     fwd, bwd = [], []
     i = 0
@@ -277,7 +333,7 @@ def launch(case, cus):
         return row_dot(case["S"], case["B"], case["log2d"])
     if f == "diag_apply":
         flags = case["tune"] | (DIAG_X_SHARED if case["shared"] else 0)
-        return diag_apply(case["dtype"], case["S"], case["B"], case["log2d"], flags)
+        return diag_apply(case["dtype"], case["S"], case["B"], case["log2d"], flags, case.get("in_place", False))
     if f == "diag_apply_bwd":
         flags = case["tune"] | (DIAG_X_SHARED if case["shared"] else 0)
         return diag_apply_bwd(case["dtype"], case["S"], case["B"], case["log2d"], flags, case["need_grad_x"], cus)
@@ -316,10 +372,11 @@ def reached(cus=256):
 
 def main():
     cus = int(sys.argv[sys.argv.index("--cus") + 1]) if "--cus" in sys.argv else 256
-    for case in CASES:
+    for case in CASES + ORDER_CASES:
         c = sized(case, cus)
         la = launch(c, cus)
-        print(f"{c['id']:40s} {la.symbol:62s} grid {la.grid} {'xcd' if la.xcd else ''}")
+        order = ORDER_NAMES[la.order] if la.order is not None else ("xcd" if la.xcd else "")
+        print(f"{c['id']:40s} {la.symbol:62s} grid {la.grid} {order}")
     print(f"{len(CASES)} cases; " + ", ".join(f"{f}: {len(s)}" for f, s in reached(cus).items()))
 
 

@@ -137,6 +137,8 @@ def _declare_f3(lib):
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
     lib.whvi_diag_apply_bwd_slabs.argtypes = [ctypes.c_int32, i64, i64, ctypes.c_int32]
+    lib.whvi_diag_apply_order.restype = ctypes.c_int32
+    lib.whvi_diag_apply_order.argtypes = [ctypes.c_int32, i64, i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
 
 
 def lib():
@@ -519,6 +521,7 @@ def wbar_bwd(grad_w: torch.Tensor, s1: torch.Tensor, u: torch.Tensor, s2: torch.
 
 DIAG_X_SHARED, DIAG_MEAN_PLUS, DIAG_RELU_IN, DIAG_RELU_OUT = 1, 2, 4, 8
 DIAG_TUNE_NT, DIAG_TUNE_CACHED, DIAG_TUNE_PLAIN_ORDER = 16, 32, 64      # tuning / cross-check flags (include/whvi_hip.h)
+DIAG_ORDER_PLAIN, DIAG_ORDER_XCD, DIAG_ORDER_SAMPLE_FASTEST = 0, 1, 2    # whvi_diag_apply_order
 
 
 def diag_apply_supported(dtype: torch.dtype, d: int) -> bool:
@@ -526,6 +529,18 @@ def diag_apply_supported(dtype: torch.dtype, d: int) -> bool:
     if dtype == torch.float32:
         return 4 <= d <= 4096 and (d & (d - 1)) == 0
     return dtype == torch.float64 and 2 <= d <= 2048 and (d & (d - 1)) == 0
+
+
+def diag_apply_order(dtype: torch.dtype, n_samples: int, batch: int, d: int, flags: int = 0, in_place: bool = False) -> int:
+    """whvi_diag_apply_order: the block order (``DIAG_ORDER_*``) of the launch ``whvi_diag_apply`` makes for ``n_samples`` x
+    ``batch`` rows of ``d`` elements with ``flags`` (``DIAG_X_SHARED`` and the tuning flags decide it).  Launches nothing."""
+    if dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("diag_apply_order: float32 / float64 only")
+    rc = int(lib().whvi_diag_apply_order(_DTYPE_CODE[dtype], int(n_samples), int(batch), int(d).bit_length() - 1, int(flags),
+                                         1 if in_place else 0))
+    if rc < 0 or d & (d - 1):
+        raise RuntimeError(f"diag_apply_order: unsupported arguments (code {rc})")
+    return rc
 
 
 def _diag_operands(x, s1, s2, u, n_samples, mean_plus, what, relu_in=False, relu_out=False):
@@ -596,10 +611,10 @@ def diag_apply_bwd(grad_out: torch.Tensor, x: torch.Tensor, s1: torch.Tensor, s2
     if S == 0 or B == 0:
         out.zero_()
         return grad_x, out
-    n_slabs = int(L.whvi_diag_apply_bwd_slabs(_DTYPE_CODE[x.dtype], S, B, log2d))
-    part = torch.empty((S, n_slabs, 2, D), dtype=x.dtype, device=x.device)
     fn = getattr(L, "whvi_diag_apply_bwd_" + _DTYPE_SUFFIX[x.dtype])
     with _OnDevice(x.device):
+        n_slabs = int(L.whvi_diag_apply_bwd_slabs(_DTYPE_CODE[x.dtype], S, B, log2d))      # (sized by x's device's CU count)
+        part = torch.empty((S, n_slabs, 2, D), dtype=x.dtype, device=x.device)
         rc = fn(None if grad_x is None else grad_x.data_ptr(), out.data_ptr(), part.data_ptr(), grad_out.data_ptr(),
                 x.data_ptr(), s1.data_ptr(), s2.data_ptr(), u.data_ptr(), None if bias is None else bias.data_ptr(), S, B, log2d,
                 n_slabs, flags | int(tune), _stream(x))

@@ -24,6 +24,13 @@ WHVI_EXPORT int64_t whvi_diag_apply_bwd_slabs(int32_t dtype, int64_t S, int64_t 
     return -1;
 }
 
+WHVI_EXPORT int32_t whvi_diag_apply_order(int32_t dtype, int64_t S, int64_t B, int32_t log2d, int32_t flags, int32_t in_place)
+{
+    if (dtype == WHVI_F32) return whvi::diag_apply_order_for<float>(S, B, log2d, flags, in_place != 0);
+    if (dtype == WHVI_F64) return whvi::diag_apply_order_for<double>(S, B, log2d, flags, in_place != 0);
+    return WHVI_ERR_ARG;
+}
+
 WHVI_EXPORT int whvi_diag_apply_bwd_f32(void *grad_x, void *out, void *part, const void *g, const void *x, const void *s1,
                                         const void *s2, const void *u, const void *bias, int64_t S, int64_t B, int32_t log2d,
                                         int64_t n_slabs, int32_t flags, void *stream)

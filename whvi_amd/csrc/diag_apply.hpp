@@ -468,6 +468,77 @@ inline int64_t diag_bwd_slabs(int64_t S, int64_t B, int rg)
     return (B + slab_rows - 1) / slab_rows;
 }
 
+// ---- the forward's launch form.  ONE place decides it: diag_apply_dispatch launches what this returns and
+// whvi_diag_apply_order (include/whvi_hip.h) reports its `order`, so a test can name the block order a launch took --
+// whvi_last_kernel cannot, the order depends on the grid and on `fastest`, both run-time values.
+constexpr int DIAG_ORDER_PLAIN = 0, DIAG_ORDER_XCD = 1, DIAG_ORDER_SAMPLE_FASTEST = 2;
+struct DiagLaunch {
+    bool nt;                     // streaming (non-temporal) instantiation
+    int k;                       // 16-byte chunks per lane: a wave's tile is 64 * k chunks, a block's four of them
+    int64_t n_chunks, n_tiles, grid;
+    uint32_t fastest;            // 8-block groups per sample when the sample index runs fastest within an XCD, else 0
+    int order;                   // DIAG_ORDER_*: what diag_apply_kernel does with blockIdx.x for these arguments
+};
+
+// The tile sizes of diag_apply_kernel as functions of a run-time log2(D): 16-byte chunks per lane of the streaming tile
+// (== pick_k<T, L>(), asserted for every L where the dispatch instantiates it), and whether the quarter-size tile exists.
+constexpr int DIAG_QUARTER_K = 4;
+template <typename T> constexpr int diag_need_k(int log2d)
+{
+    return log2d > ilog2(Elem<T>::VEC) + 6 ? 1 << (log2d - ilog2(Elem<T>::VEC) - 6) : 1;      // chunks per lane that hold one row
+}
+template <typename T> constexpr int diag_big_k(int log2d)
+{
+    return diag_need_k<T>(log2d) > pick_k<T, ilog2(Elem<T>::VEC)>() ? diag_need_k<T>(log2d) : pick_k<T, ilog2(Elem<T>::VEC)>();
+}
+template <typename T> constexpr bool diag_has_quarter(int log2d)
+{
+    return diag_need_k<T>(log2d) <= DIAG_QUARTER_K && DIAG_QUARTER_K < diag_big_k<T>(log2d);
+}
+
+// S * B >= 1 rows of 2^log2d elements, log2d inside the supported range (the callers check both)
+template <typename T>
+inline DiagLaunch diag_apply_launch(int64_t S, int64_t B, int32_t log2d, int32_t flags, bool in_place)
+{
+    const bool shared = (flags & WHVI_DIAG_X_SHARED) != 0;
+    const int64_t rows = S * B;
+    DiagLaunch la;
+    // x is not counted when it is shared (B rows against S * B written) or when the launch is in place
+    la.nt = (flags & WHVI_DIAG_TUNE_NT) ? true : (flags & WHVI_DIAG_TUNE_CACHED) ? false
+            : stream_sized((rows << log2d) * (int64_t)sizeof(T), in_place || shared);
+    la.k = diag_big_k<T>(log2d);                                  // pick_k<T, log2d>(): one row, at least the 64-register tile
+    /* cache-resident results, rows of up to 256 chunks (f32 D <= 1024): quarter-size tiles -- four times the waves with a
+       quarter of the work each, as for the weight kernels (wbar_fwd.hpp): config 2 60 -> 50-53 us, D = 1024 +5 %, D = 64
+       +9 %; NOT for one-row tiles of half the size (D = 2048: 34 -> 57 us).  WHVI_DIAG_TUNE_BIG_TILES: A/B */
+    if (diag_has_quarter<T>(log2d) && !la.nt && !(flags & WHVI_DIAG_TUNE_BIG_TILES)) la.k = DIAG_QUARTER_K;
+    la.n_chunks = (rows << log2d) / Elem<T>::VEC;
+    la.n_tiles = (la.n_chunks + 64 * la.k - 1) / (64 * la.k);
+    la.grid = (la.n_tiles + 3) / 4;
+    /* shared input: sample index fastest within an XCD when every sample is a whole number of 8-block groups */
+    const int64_t blk_chunks = (int64_t)4 * 64 * la.k, per_sample = (B << log2d) / Elem<T>::VEC;
+    /* (streaming launches only: at cache-resident sizes -- config 2's 256 MiB -- the plain order is faster, 54 vs 64 us) */
+    la.fastest = (shared && la.nt && S > 1 && !(flags & WHVI_DIAG_TUNE_PLAIN_ORDER) && per_sample % (8 * blk_chunks) == 0)
+                     ? (uint32_t)(per_sample / (8 * blk_chunks)) : 0u;
+    la.order = la.fastest != 0u ? DIAG_ORDER_SAMPLE_FASTEST : (la.nt && (la.grid & 7) == 0) ? DIAG_ORDER_XCD : DIAG_ORDER_PLAIN;
+    return la;
+}
+
+constexpr int32_t DIAG_FLAGS = WHVI_DIAG_X_SHARED | WHVI_DIAG_MEAN_PLUS | WHVI_DIAG_RELU_IN | WHVI_DIAG_RELU_OUT | WHVI_DIAG_TUNE_MASK;
+
+// whvi_diag_apply_order: the order of the launch whvi_diag_apply makes for these arguments, or the error code it returns
+// before launching anything.  Launches nothing, touches no device.
+template <typename T>
+inline int diag_apply_order_for(int64_t S, int64_t B, int32_t log2d, int32_t flags, bool in_place)
+{
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    if (S < 0 || B < 0 || (flags & ~DIAG_FLAGS)) return WHVI_ERR_ARG;
+    if (log2d < LV || log2d > diag_max_log2d<T>()) return WHVI_ERR_SIZE;
+    if (S * B == 0) return DIAG_ORDER_PLAIN;                      // nothing to launch
+    if (S * B >= ((int64_t)1 << 32)) return WHVI_ERR_SIZE;
+    if (in_place && (flags & WHVI_DIAG_X_SHARED)) return WHVI_ERR_OVERLAP;
+    return diag_apply_launch<T>(S, B, log2d, flags, in_place).order;
+}
+
 template <typename T>
 inline int diag_apply_dispatch(void *dst, const void *x, const void *s1, const void *s2, const void *u, const void *bias,
                                int64_t S, int64_t B, int32_t log2d, int32_t flags, void *stream)
@@ -475,7 +546,7 @@ inline int diag_apply_dispatch(void *dst, const void *x, const void *s1, const v
     constexpr int LV = ilog2(Elem<T>::VEC);
     g_err[0] = 0;
     if (S < 0 || B < 0) return fail(WHVI_ERR_ARG, "whvi_diag_apply: negative size%s", "");
-    if (flags & ~(WHVI_DIAG_X_SHARED | WHVI_DIAG_MEAN_PLUS | WHVI_DIAG_RELU_IN | WHVI_DIAG_RELU_OUT | WHVI_DIAG_TUNE_MASK))
+    if (flags & ~DIAG_FLAGS)
         return fail(WHVI_ERR_ARG, "whvi_diag_apply: unknown flags%s 0x%llx", "", flags);
     if (log2d < LV || log2d > diag_max_log2d<T>())
         return fail(WHVI_ERR_SIZE, "whvi_diag_apply: log2(D)%s = %lld is outside the supported range [%lld, ...]", "", log2d, LV);
@@ -496,40 +567,31 @@ inline int diag_apply_dispatch(void *dst, const void *x, const void *s1, const v
     const uint32_t mean_plus = ((flags & WHVI_DIAG_MEAN_PLUS) ? DIAG_OPT_MEAN : 0u) | ((flags & WHVI_DIAG_RELU_IN) ? DIAG_OPT_RELU_IN : 0u) |
                                ((flags & WHVI_DIAG_RELU_OUT) ? DIAG_OPT_RELU_OUT : 0u);       // the kernels' option word
     const FastDiv db = make_fastdiv((uint32_t)B);
+    const DiagLaunch la = diag_apply_launch<T>(S, B, log2d, flags, dst == x);
 #define WHVI_DIAG(L, NT, SH) WHVI_DIAG_K(L, NT, SH, (pick_k<T, L>()))
 #define WHVI_DIAG_K(L, NT, SH, KK)                                                                              \
     do {                                                                                                        \
         constexpr int K_ = KK;                                                                                  \
-        const int64_t n_chunks = (rows << L) / Elem<T>::VEC, n_tiles = (n_chunks + 64 * K_ - 1) / (64 * K_);    \
-        /* shared input: sample index fastest within an XCD when every sample is a whole number of 8-block groups */ \
-        const int64_t blk_chunks = (int64_t)4 * 64 * K_, per_sample = (B << L) / Elem<T>::VEC;                  \
-        /* (streaming launches only: at cache-resident sizes -- config 2's 256 MiB -- the plain order is faster, 54 vs 64 us) */ \
-        const uint32_t fastest = (SH && NT && S > 1 && !(flags & WHVI_DIAG_TUNE_PLAIN_ORDER) && per_sample % (8 * blk_chunks) == 0) \
-                                     ? (uint32_t)(per_sample / (8 * blk_chunks)) : 0u;                          \
         note_launch<T>("diag_apply_kernel", L, K_, (bool)NT, (bool)SH);                                         \
-        hipLaunchKernelGGL((diag_apply_kernel<T, L, K_, NT, SH>), dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, st, \
+        hipLaunchKernelGGL((diag_apply_kernel<T, L, K_, NT, SH>), dim3((unsigned)la.grid), dim3(256), 0, st,    \
                            (u32x4 *)dst, (const u32x4 *)x, (const T *)s1, (const T *)s2, (const T *)u, (const T *)bias, \
-                           n_chunks, n_tiles, (uint32_t)rows, db, mean_plus, fastest);                          \
+                           la.n_chunks, la.n_tiles, (uint32_t)rows, db, mean_plus, la.fastest);                 \
     } while (0)
 #define WHVI_CASE(L)                                                                                            \
     case L:                                                                                                     \
         if constexpr (L >= LV && L <= diag_max_log2d<T>()) {                                                    \
-            const bool nt = (flags & WHVI_DIAG_TUNE_NT) ? true : (flags & WHVI_DIAG_TUNE_CACHED) ? false           \
-                            : stream_sized((rows << L) * (int64_t)sizeof(T), dst, shared ? nullptr : x);        \
-            /* cache-resident results, rows of up to 256 chunks (f32 D <= 1024): quarter-size tiles -- four times the waves with a \
-               quarter of the work each, as for the weight kernels (wbar_fwd.hpp): config 2 60 -> 50-53 us, D = 1024 +5 %, D = 64 \
-               +9 %; NOT for one-row tiles of half the size (D = 2048: 34 -> 57 us).  WHVI_DIAG_TUNE_BIG_TILES: A/B */    \
-            constexpr int NEED_ = (L > LV + 6) ? (1 << (L - LV - 6)) : 1;                                       \
-            constexpr int KS_ = 4;                                                                              \
+            /* la.k is one of the two tile sizes instantiated here: the run-time rule is the compile-time one */ \
+            static_assert(diag_big_k<T>(L) == pick_k<T, L>(), "diag_apply_launch and pick_k disagree on the tile size"); \
+            constexpr int KS_ = DIAG_QUARTER_K;                                                                 \
             /* (a compile-time guard: the quarter tiles of rows longer than one of them are never launched, so never built) */ \
-            if constexpr (NEED_ <= KS_ && KS_ < pick_k<T, L>()) {                                               \
-                if (!nt && !(flags & WHVI_DIAG_TUNE_BIG_TILES)) {                                               \
+            if constexpr (diag_has_quarter<T>(L)) {                                                             \
+                if (la.k == KS_) {                                                                              \
                     if (shared) WHVI_DIAG_K(L, false, true, KS_); else WHVI_DIAG_K(L, false, false, KS_);       \
                     break;                                                                                      \
                 }                                                                                               \
             }                                                                                                   \
-            if (shared) { if (nt) WHVI_DIAG(L, true, true); else WHVI_DIAG(L, false, true); }                   \
-            else { if (nt) WHVI_DIAG(L, true, false); else WHVI_DIAG(L, false, false); }                        \
+            if (shared) { if (la.nt) WHVI_DIAG(L, true, true); else WHVI_DIAG(L, false, true); }                \
+            else { if (la.nt) WHVI_DIAG(L, true, false); else WHVI_DIAG(L, false, false); }                     \
         }                                                                                                       \
         break;
     switch (log2d) {

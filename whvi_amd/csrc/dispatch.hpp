@@ -129,9 +129,10 @@ constexpr int64_t NT_MIN_BYTES = (int64_t)256 << 20;
 // destination otherwise -- EXCEEDS the 256 MiB Infinity Cache.  Measured crossover (tools/probe_nt_threshold.py,
 // D = 4096 f32): in place, cached accesses win up to 256 MiB (6.7 vs 5.7 TB/s) and lose from 320 MiB (5.7 vs 5.8);
 // out of place they win up to 128 MiB per buffer (7.3 vs 5.4) and lose from 192 MiB (5.2 vs 5.7).
+inline bool stream_sized(int64_t bytes, bool counted_once) { return (counted_once ? bytes : 2 * bytes) > NT_MIN_BYTES; }
 inline bool stream_sized(int64_t bytes, const void *dst, const void *src)
 {
-    return (dst == src || src == nullptr ? bytes : 2 * bytes) > NT_MIN_BYTES;
+    return stream_sized(bytes, dst == src || src == nullptr);
 }
 
 // Streaming launch of the f32 one-row tile of 128 data registers (D = 8192) at THREE waves per SIMD.  Defined -- with its
