@@ -194,6 +194,35 @@ int whvi_fused_shs_ex_f64(void *dst, const void *src, const void *a, const void 
                           int64_t sample_stride, int64_t group_rows, int32_t axis,
                           int32_t flags, void *stream);
 
+/* Backward of whvi_fused_shs_f32 with axis = WHVI_AXIS_COL, shared a / c and per-sample b -- y = a (.) H(b_s (.) H(c (.) x)),
+ * the fastfood layer -- in ONE launch plus a tiny finishing launch inside the same call.  float32.  Rows are in (sample, row, D)
+ * order: n_samples * sample_stride rows, sample s holds rows [s * sample_stride, (s + 1) * sample_stride).  Per row:
+ *     t1 = H(c x) (recomputed);  u = H(b_s t1), grad_a += grad_y u;  v = H(a grad_y), grad_b[s] += v t1;
+ *     w = H(b_s v), grad_c += w x;  grad_x = c w
+ *   grad_x : (n_samples * sample_stride, D), or NULL to skip the store.  Every multiply of its chain is its own rounding and the
+ *            butterflies are the forward's: bit for bit whvi_fused_shs_f32(grad_x, grad_y, a := c, b, c := a, ...).
+ *   grad_a, grad_c : (D), summed over all rows;  grad_b : (n_samples, D), summed over each sample's rows.  The sums are fused
+ *            multiply-adds into registers; every block writes one partial per field to `work` and the finishing launch adds them
+ *            in ascending block order: no atomics, bit-identical on every run.
+ *   grad_y : (n_samples * sample_stride, D).  x : the same, or with flags = WHVI_FUSED_SRC_SHARED (sample_stride, D): row r of
+ *            every sample reads x[r] (grad_x is still written per (sample, row): the caller sums over samples).
+ *   a, c : (D);  b : (n_samples, D).
+ *   work   : whvi_fused_shs_bwd_workspace(n_samples, sample_stride, log2d) bytes.  The query needs no device and depends on its
+ *            arguments alone: 12 * D bytes per block of the launch, n_samples * n_slabs blocks, where the slabs per sample aim
+ *            at 1024 blocks in all (512 at log2d = 12) and never go below four wave tiles (max(1, 1024 / D) rows each) per
+ *            slab.  0 when n_samples * sample_stride == 0; WHVI_ERR_ARG for a negative size, WHVI_ERR_SIZE outside the range.
+ * Supported: 6 <= log2d <= 12 -- whvi_fused_shs_bwd_supported(log2d) returns 1 exactly then (no device needed), the call
+ * WHVI_ERR_SIZE otherwise.  flags other than 0 / WHVI_FUSED_SRC_SHARED: WHVI_ERR_ARG ("unknown fused flags").  Only grad_x may be
+ * NULL (WHVI_ERR_ARG); every pointer 16-byte aligned (WHVI_ERR_ALIGN); grad_x, the parameter gradients and the workspace must
+ * not overlap an input (WHVI_ERR_OVERLAP).  n_samples * sample_stride == 0 returns WHVI_OK without a launch or a write.  Every
+ * argument check runs before any device call.  No allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_shs_bwd_kernel<float, log2d, K, NT>. */
+int     whvi_fused_shs_bwd_supported(int32_t log2d);
+int64_t whvi_fused_shs_bwd_workspace(int64_t n_samples, int64_t sample_stride, int32_t log2d);
+int     whvi_fused_shs_bwd_f32(void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                               const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                               int64_t n_samples, int64_t sample_stride, int32_t log2d, int32_t flags, void *stream);
+
 /* The same pipeline on 16-bit ACTIVATION streams: dst / src are IEEE half (_f16) or bfloat16 (_bf16), in place or out of
  * place; a, b, c are FLOAT32 vectors (they are the layer's float32 parameters; nothing is gained by rounding them).  Each
  * element is converted to f32 exactly, every multiply is its own f32 rounding, the butterflies are f32 adds / subs in the

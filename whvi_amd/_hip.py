@@ -133,6 +133,12 @@ def _declare_f3(lib):
     lib.whvi_mlp_fastfood_apply_bwd_f32.restype = ctypes.c_int
     lib.whvi_mlp_fastfood_apply_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp,
                                                     i32, vp, i64, i64, i32, i32, i32, vp]
+    lib.whvi_fused_shs_bwd_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_bwd_supported.argtypes = [i32]
+    lib.whvi_fused_shs_bwd_workspace.restype = i64
+    lib.whvi_fused_shs_bwd_workspace.argtypes = [i64, i64, i32]
+    lib.whvi_fused_shs_bwd_f32.restype = ctypes.c_int
+    lib.whvi_fused_shs_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -368,6 +374,55 @@ def fused_shs(src, a=None, b=None, c=None, *, axis: str = "col", n_samples: int 
                 sample_stride, group_rows, ax, flags, _stream(out))
     _check(rc, "whvi_fused_shs")
     return out
+
+
+def fused_shs_bwd_supported(dtype: torch.dtype, d: int) -> bool:
+    """Row lengths the one-launch backward of the fused pipeline covers (``whvi_fused_shs_bwd_supported``): float32,
+    64 <= D <= 4096."""
+    if dtype != torch.float32 or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return bool(lib().whvi_fused_shs_bwd_supported(d.bit_length() - 1))
+
+
+def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int,
+                  sample_stride: int, shared: bool = False, need_x: bool = True):
+    """Backward of ``y = a * fwht(b_s * fwht(c * x))`` in one call (whvi_fused_shs_bwd_f32): ``(grad_x | None, grad_a (D),
+    grad_b (S, D), grad_c (D))`` from ``grad_y`` ``(S * sample_stride, D)`` in (sample, row) order and the forward's operands.
+    ``shared``: ``x`` is ``(sample_stride, D)``, read by every sample; ``grad_x`` still has ``S * sample_stride`` rows (the
+    caller sums over samples).  ``need_x=False`` allocates and writes no ``grad_x``.  The workspace comes from torch's
+    allocator, sized by ``whvi_fused_shs_bwd_workspace``."""
+    S, stride = int(n_samples), int(sample_stride)
+    if grad_y.device.type != "cuda" or grad_y.dim() != 2:
+        raise RuntimeError("fused_shs_bwd: grad_y must be a 2-D CUDA tensor")
+    rows, d = grad_y.shape
+    if any(t.device != grad_y.device or t.dtype != torch.float32 for t in (grad_y, x, a, b, c)):
+        raise RuntimeError("fused_shs_bwd: float32 CUDA tensors on one device only")
+    if not fused_shs_bwd_supported(torch.float32, d):
+        raise RuntimeError(f"fused_shs_bwd: rows of {d} elements are outside the supported range 64 .. 4096")
+    if (rows != S * stride or tuple(x.shape) != ((stride if shared else rows), d) or a.numel() != d or c.numel() != d
+            or b.numel() != S * d):
+        raise RuntimeError("fused_shs_bwd: operand shapes do not match (rows must be n_samples * sample_stride)")
+    grad_y, x, a, b, c = (_aligned(t) for t in (grad_y, x, a.reshape(-1), b.reshape(-1), c.reshape(-1)))
+    dev = grad_y.device
+    grad_x = torch.empty((rows, d), dtype=torch.float32, device=dev) if need_x else None
+    grad_a = torch.empty((d,), dtype=torch.float32, device=dev)
+    grad_b = torch.empty((S, d), dtype=torch.float32, device=dev)
+    grad_c = torch.empty((d,), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return grad_x, grad_a.zero_(), grad_b.zero_(), grad_c.zero_()
+    L = lib()
+    log2d = d.bit_length() - 1
+    n = int(L.whvi_fused_shs_bwd_workspace(S, stride, log2d))
+    if n < 0:
+        raise RuntimeError(f"whvi_fused_shs_bwd_workspace failed (code {n})")
+    work = torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+    with _OnDevice(dev):
+        rc = L.whvi_fused_shs_bwd_f32(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(),
+                                      grad_c.data_ptr(), work.data_ptr(), grad_y.data_ptr(), x.data_ptr(), a.data_ptr(),
+                                      b.data_ptr(), c.data_ptr(), S, stride, log2d, FUSED_SRC_SHARED if shared else 0,
+                                      _stream(grad_y))
+    _check(rc, "whvi_fused_shs_bwd")
+    return grad_x, grad_a, grad_b, grad_c
 
 
 def reparam_kl(g_mu: torch.Tensor, g_rho: torch.Tensor, eps: torch.Tensor, lambda_: float):

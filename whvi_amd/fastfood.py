@@ -95,12 +95,19 @@ class FastfoodFunction(torch.autograd.Function):
     launch and returns ``x.dtype``; so is a backward that wants ``grad_x`` alone (``a`` and ``c`` exchanged).  A backward that
     wants a parameter gradient upcasts ``x`` and ``grad_y`` to float32 once -- 2 bytes read + 4 written per element each, and
     every pass behind them moves 4-byte elements -- runs the float32 code below, and returns float32 parameter gradients
-    and ``grad_x`` cast to ``x.dtype``."""
+    and ``grad_x`` cast to ``x.dtype``.
+
+    ``fused_backward`` (float32 CUDA tensors, 64 <= D <= 4096, rows == n_samples * sample_stride, at least one of ``a, b, c``
+    wanting a gradient): the backward is ONE launch of ``whvi_fused_shs_bwd_f32`` -- ``x`` and ``grad_y`` read once, ``grad_x``
+    written once, no activation-sized temporary -- plus the sum over samples for a shared ``x``.  ``grad_x`` has the bits of
+    the chain's; the parameter gradients are the same sums in another order.  Everything else -- host tensors,
+    other dtypes or sizes, ``grad_x`` alone -- runs the code below unchanged."""
 
     @staticmethod
-    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False):
+    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False):
         """``shared``: ``x`` is ``(sample_stride, D)``, the same rows for every sample (a layer's first Monte-Carlo pass on
-        a ``(batch, D)`` input); the result still has ``n_samples * sample_stride`` rows."""
+        a ``(batch, D)`` input); the result still has ``n_samples * sample_stride`` rows.  ``fused_backward``: see the class."""
+        ctx.fused_backward = bool(fused_backward) and x.device.type == "cuda"
         ctx.save_for_backward(x, a, b, c)
         ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
         ctx.keep_half = bool(keep_half) and x.device.type == "cuda" and x.dtype in _HALF
@@ -117,8 +124,20 @@ class FastfoodFunction(torch.autograd.Function):
         x_dtype = x.dtype
         if ctx.keep_half:
             if need_x and not (need_a or need_b or need_c or ctx.shared):
-                return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None, None, None, None, None
+                return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None, None, None, None, None, None
             x, grad_y = x.float(), grad_y.float()
+        if (ctx.fused_backward and not ctx.keep_half and (need_a or need_b or need_c) and x.dtype == torch.float32 and grad_y.dtype == torch.float32
+                and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
+                and grad_y.size(0) == S * stride):
+            from whvi_amd import _hip
+            if _hip.fused_shs_bwd_supported(torch.float32, x.size(1)):
+                # ONE launch: t1, u, v, w stay in registers, the three sums leave the chip as one partial per block
+                grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
+                                                                    need_x=need_x)
+                if ctx.shared and grad_x is not None:
+                    grad_x = grad_x.view(S, stride, -1).sum(dim=0)
+                return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
+                        grad_c if need_c else None, None, None, None, None, None)
         if ctx.shared:
             # every sample read the same rows: their gradients add up (what autograd does for an expanded input)
             fold = lambda g: None if g is None else g.view(S, stride, -1).sum(dim=0)   # noqa: E731
@@ -126,7 +145,7 @@ class FastfoodFunction(torch.autograd.Function):
         else:
             fold = lambda g: g                                                        # noqa: E731
         if need_x and not (need_a or need_b or need_c):
-            return fold(_pipeline(grad_y, c, b, a, S, stride)).to(x_dtype), None, None, None, None, None, None, None
+            return fold(_pipeline(grad_y, c, b, a, S, stride)).to(x_dtype), None, None, None, None, None, None, None, None
         # Every transform of the backward pass is "scale, then FWHT" (optionally scaled again): ONE launch each through the
         # one-transform form of the fused kernel where it exists, the multiply + plain transform elsewhere -- the same
         # roundings either way (tests/test_streaming_parity_gpu.py pins the launch to multiply + fwht_rows bit for bit)
@@ -147,13 +166,14 @@ class FastfoodFunction(torch.autograd.Function):
                 grad_c = (w * x).sum(dim=0)
             if need_x:
                 grad_x = fold(c * w).to(x_dtype)
-        return grad_x, grad_a, grad_b, grad_c, None, None, None, None
+        return grad_x, grad_a, grad_b, grad_c, None, None, None, None, None
 
 
 class WHVIFastfoodMatrix(nn.Module):
     """Square (D, D) WHVI layer in fastfood mode (see the module docstring): parameters ``s1, s2, g_mu, g_rho``
     (+ optional ``bias``) as in ``WHVISquarePow2Matrix``; ``forward(x)`` draws one eps, ``forward_mc(x, S)`` draws S
     and runs all samples in one launch."""
+    fused_backward = False    # float32 CUDA activations, 64 <= D <= 4096: True = the backward is one launch (FastfoodFunction); False: the chain
     keep_half = False         # float16 / bfloat16 CUDA activations: True = one 16-bit launch, output in the input's dtype (False: promoted to float32)
 
     def __init__(self, D, lambda_=1e-5, bias=False):
@@ -203,12 +223,13 @@ class WHVIFastfoodMatrix(nn.Module):
         if x.dim() == 2:
             # a (batch, D) input shared by all samples: read by every sample straight from the caches, never expanded
             batch = x.size(0)
-            out = FastfoodFunction.apply(x.contiguous(), self.s1, g, self.s2, n_samples, batch, True, half)
+            out = FastfoodFunction.apply(x.contiguous(), self.s1, g, self.s2, n_samples, batch, True, half, self.fused_backward)
             out = out.view(n_samples, batch, self.D)
             return out + bias if bias is not None else out
         batch = x.size(1)
         rows = x.reshape(n_samples * batch, self.D).contiguous()
-        out = FastfoodFunction.apply(rows, self.s1, g, self.s2, n_samples, batch, False, half).view(n_samples, batch, self.D)
+        out = FastfoodFunction.apply(rows, self.s1, g, self.s2, n_samples, batch, False, half,
+                                     self.fused_backward).view(n_samples, batch, self.D)
         return out + bias if bias is not None else out
 
     def forward(self, x):
