@@ -128,10 +128,14 @@ def test_training_plan_reasons_on_host_tensors():
     assert fused_fastfood.plan(_net(3, 128, modes=["reference"]), x, 4, training=True) == \
         "no fastfood square layer (mode='fastfood'): the reference-mode networks are fused_mlp's"
     assert "range" in fused_fastfood.plan(_net(3, 4096), x, 4, training=True)
-    src = open(os.path.join(ROOT, "whvi_amd", "fused_fastfood.py")).read()
-    assert '"an autograd graph is wanted (the fused fastfood pass has no backward)"' in src
-    assert "no autograd graph is wanted (the training pass is for passes that need one)" in src
-    assert "is outside whvi_mlp_fastfood_apply_bwd's range" in src
+    # whole strings, from what plan() returns: a host input is refused first, a network outside the forward's range by match.
+    # The reasons behind the device check (graph wanted / not wanted, the backward's range) are asserted with == on the GPU:
+    # tests/test_fused_refusals_gpu.py
+    for training in (True, False):
+        with torch.set_grad_enabled(training):
+            assert fused_fastfood.plan(net, x, 4, training=training) == "input: needs a float32 CUDA (batch, 3) tensor"
+            assert fused_fastfood.plan(_net(3, 4096), x, 4, training=training) == \
+                "hidden width 4096 with 1 fastfood layers is outside whvi_mlp_fastfood_apply's range"
 
 
 # the dispatch of whvi_mlp_fastfood_apply_bwd_f32 (mlp_fastfood_apply_bwd.hpp), restated

@@ -105,34 +105,20 @@ def _declare_f3(lib):
     lib.whvi_row_dot_f32.restype = ctypes.c_int
     lib.whvi_row_dot_f32.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.c_int32, ctypes.c_int32, vp]
     i32 = ctypes.c_int32
-    lib.whvi_mlp_apply_supported.restype = ctypes.c_int
-    lib.whvi_mlp_apply_supported.argtypes = [i32, i32, i32]
-    lib.whvi_mlp_apply_f32.restype = ctypes.c_int
-    lib.whvi_mlp_apply_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, vp]
-    lib.whvi_mlp_apply_bwd_supported.restype = ctypes.c_int
-    lib.whvi_mlp_apply_bwd_supported.argtypes = [i32, i32, i32]
-    lib.whvi_mlp_apply_bwd_workspace.restype = i64
-    lib.whvi_mlp_apply_bwd_workspace.argtypes = [i64, i64, i32, i32, i32]
-    lib.whvi_mlp_apply_bwd_f32.restype = ctypes.c_int
-    lib.whvi_mlp_apply_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64, i64,
-                                           i32, i32, vp]
-    lib.whvi_mlp_apply_act_f32.restype = ctypes.c_int
-    lib.whvi_mlp_apply_act_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32, vp]
-    lib.whvi_mlp_apply_act_bwd_f32.restype = ctypes.c_int
-    lib.whvi_mlp_apply_act_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, i64,
-                                               i64, i32, i32, i32, vp]
-    lib.whvi_mlp_fastfood_apply_supported.restype = ctypes.c_int
-    lib.whvi_mlp_fastfood_apply_supported.argtypes = [i32, i32, i32]
-    lib.whvi_mlp_fastfood_apply_f32.restype = ctypes.c_int
-    lib.whvi_mlp_fastfood_apply_f32.argtypes = [vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, i64, i64, i32, i32, i32,
-                                                vp]
-    lib.whvi_mlp_fastfood_apply_bwd_supported.restype = ctypes.c_int
-    lib.whvi_mlp_fastfood_apply_bwd_supported.argtypes = [i32, i32, i32]
-    lib.whvi_mlp_fastfood_apply_bwd_workspace.restype = i64
-    lib.whvi_mlp_fastfood_apply_bwd_workspace.argtypes = [i64, i64, i32, i32, i32]
-    lib.whvi_mlp_fastfood_apply_bwd_f32.restype = ctypes.c_int
-    lib.whvi_mlp_fastfood_apply_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp,
-                                                    i32, vp, i64, i64, i32, i32, i32, vp]
+    # the six network entry points share one operand block: x, first, w_in, b_in, n_mid, s1, s2, u / g, b_mid, mid_bias, w_out
+    net = [vp, i32, vp, vp, i32, vp, vp, vp, vp, i32, vp]
+    dims = [i64, i64, i32]                                              # S, B, log2d
+    for name in ("mlp_apply", "mlp_fastfood_apply"):
+        for query, restype, argtypes in (("_supported", ctypes.c_int, [i32, i32, i32]), ("_bwd_supported", ctypes.c_int, [i32, i32, i32]),
+                                         ("_bwd_workspace", i64, [i64, i64, i32, i32, i32])):
+            fn = getattr(lib, "whvi_" + name + query)
+            fn.restype, fn.argtypes = restype, argtypes
+    # (entry point, gradient outputs + workspace in front of the backward's work_floats and g, trailing act / act_bits words)
+    for name, n_out, n_flags in (("mlp_apply", 6, 1), ("mlp_apply_act", 6, 2), ("mlp_fastfood_apply", 8, 2)):
+        fwd, bwd = getattr(lib, "whvi_" + name + "_f32"), getattr(lib, "whvi_" + name + "_bwd_f32")
+        fwd.restype = bwd.restype = ctypes.c_int
+        fwd.argtypes = [vp] + net + [vp] + dims + [i32] * n_flags + [vp]           # y, ..., b_out, ..., stream
+        bwd.argtypes = [vp] * n_out + [i64, vp] + net + dims + [i32] * n_flags + [vp]
     lib.whvi_fused_shs_bwd_supported.restype = ctypes.c_int
     lib.whvi_fused_shs_bwd_supported.argtypes = [i32]
     lib.whvi_fused_shs_bwd_workspace.restype = i64
@@ -226,6 +212,11 @@ def _aligned(t: torch.Tensor) -> torch.Tensor:
     if t.data_ptr() % 16 != 0:
         t = t.clone(memory_format=torch.contiguous_format)
     return t
+
+
+def _require_f32_on_one_device(what: str, dev, ops):
+    if dev.type != "cuda" or any(t.device != dev or t.dtype != torch.float32 for t in ops):
+        raise RuntimeError(f"{what}: float32 CUDA tensors on one device only")
 
 
 FWHT_SIGNED_LANES = 1 << 23      # whvi_fwht_ex variant bit (include/whvi_hip.h): faster f32 / f64 streams, -0 results become +0
@@ -395,8 +386,7 @@ def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: tor
     if grad_y.device.type != "cuda" or grad_y.dim() != 2:
         raise RuntimeError("fused_shs_bwd: grad_y must be a 2-D CUDA tensor")
     rows, d = grad_y.shape
-    if any(t.device != grad_y.device or t.dtype != torch.float32 for t in (grad_y, x, a, b, c)):
-        raise RuntimeError("fused_shs_bwd: float32 CUDA tensors on one device only")
+    _require_f32_on_one_device("fused_shs_bwd", grad_y.device, (grad_y, x, a, b, c))
     if not fused_shs_bwd_supported(torch.float32, d):
         raise RuntimeError(f"fused_shs_bwd: rows of {d} elements are outside the supported range 64 .. 4096")
     if (rows != S * stride or tuple(x.shape) != ((stride if shared else rows), d) or a.numel() != d or c.numel() != d
@@ -742,12 +732,70 @@ def _mlp_act(act: str) -> int:
     return MLP_ACTS[act]
 
 
-def mlp_apply_supported(first: int, n_mid: int, d: int) -> bool:
-    """The rule of ``whvi_mlp_apply_supported`` (include/whvi_hip.h), restated so that it needs no library: first-layer kind
-    1 / 4 / 8, 1 .. 4 square layers, D = 64 .. 2048 a power of two, and one sample's operands -- 4 D (K + 2 + 2 n_mid) bytes
-    -- within 64 KiB of LDS."""
+def _mlp_supported(first: int, n_mid: int, d: int, vectors: int) -> bool:
+    """First-layer kind 1 / 4 / 8, 1 .. 4 square layers, D = 64 .. 2048 a power of two, and one sample's operands -- 4 D
+    (K + 2 + ``vectors`` n_mid) bytes, ``vectors`` D-vectors per square layer -- within 64 KiB of LDS."""
     return (first in (MLP_FIRST_COLUMN, MLP_FIRST_K4, MLP_FIRST_K8) and 1 <= n_mid <= 4 and 64 <= d <= 2048
-            and (d & (d - 1)) == 0 and 4 * d * (first + 2 + 2 * n_mid) <= 65536)
+            and (d & (d - 1)) == 0 and 4 * d * (first + 2 + vectors * n_mid) <= 65536)
+
+
+def mlp_apply_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_apply_supported`` (include/whvi_hip.h), restated so that it needs no library: ``_mlp_supported``
+    with 2 vectors per square layer (its diagonal and its bias)."""
+    return _mlp_supported(first, n_mid, d, 2)
+
+
+def mlp_fastfood_apply_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_fastfood_apply_supported`` (include/whvi_hip.h) without the library: ``_mlp_supported`` with 4
+    vectors per square layer (s1, s2, g_k and the bias)."""
+    return _mlp_supported(first, n_mid, d, 4)
+
+
+def mlp_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_apply_bwd_supported`` (include/whvi_hip.h) without the library: ``mlp_apply_supported`` with at
+    most 2 square layers and D <= 1024."""
+    return mlp_apply_supported(first, n_mid, d) and n_mid <= 2 and d <= 1024
+
+
+def mlp_fastfood_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
+    """The rule of ``whvi_mlp_fastfood_apply_bwd_supported`` (include/whvi_hip.h) without the library:
+    ``mlp_fastfood_apply_supported`` with at most 2 square layers and D <= 1024."""
+    return mlp_fastfood_apply_supported(first, n_mid, d) and n_mid <= 2 and d <= 1024
+
+
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _mlp_operands(what, supported, act, x, w_in, b_in, s1, s2, mid, mid_rows, b_mid, mid_bias, w_out, b_out=None, g=None):
+    """The operands of the four network launches, checked once: ``what`` names the caller in every refusal, ``supported`` is
+    its range rule, ``mid`` the per-layer tensor, expected as ``(n_mid, mid_rows, D)`` with ``mid_rows`` counted beyond S (1 for
+    ``u`` and its mean row, 0 for ``g``).  ``g`` = dL/dy (S, B) is the backward's extra operand; a backward has no ``b_out``.
+    Returns ``(code, first, n_mid, S, B, D, args, keep)``: the activation code, the sizes, the C entry points' shared argument
+    block ([g,] x .. w_out[, b_out], S, B, log2d) and the contiguous, aligned tensors behind its pointers, which the caller
+    holds until it has launched."""
+    code = _mlp_act(act)
+    S, D = w_out.shape
+    n_mid = s1.shape[0]
+    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
+    if not supported(first, n_mid, D):
+        raise RuntimeError(f"{what}: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
+    ops = (x, w_in, s1, s2, mid, w_out) + tuple(t for t in (g, b_in, b_mid, b_out) if t is not None)
+    _require_f32_on_one_device(what, x.device, ops)
+    B = x.shape[0]
+    if ((g is not None and tuple(g.shape) != (S, B)) or tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D)
+            or tuple(s1.shape) != (n_mid, D) or tuple(s2.shape) != (n_mid, D) or tuple(mid.shape) != (n_mid, S + mid_rows, D)
+            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)
+            or (b_out is not None and b_out.numel() != 1)):
+        raise RuntimeError(f"{what}: operand shapes do not match")
+    if g is not None:
+        g = _aligned(g)
+    x, w_in, s1, s2, mid, w_out = (_aligned(t) for t in (x, w_in, s1, s2, mid, w_out))
+    b_in, b_mid, b_out = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid, b_out))
+    args = (x.data_ptr(), first, w_in.data_ptr(), _ptr(b_in), n_mid, s1.data_ptr(), s2.data_ptr(), mid.data_ptr(), _ptr(b_mid),
+            int(mid_bias), w_out.data_ptr())
+    args = args + (_ptr(b_out),) if g is None else (g.data_ptr(),) + args
+    return code, first, n_mid, S, B, D, args + (S, B, D.bit_length() - 1), (g, x, w_in, s1, s2, mid, w_out, b_in, b_mid, b_out)
 
 
 def mlp_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor, u: torch.Tensor, b_mid,
@@ -758,44 +806,16 @@ def mlp_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: t
     ``mid_bias`` bit m: square layer m has a bias; ``relu``: the boundaries that carry the activation ``act`` -- bit 0 behind
     the first layer, bit 1 + m behind square layer m.  ``act``: "relu" (whvi_mlp_apply_f32), "sigmoid" or "tanh"
     (whvi_mlp_apply_act_f32)."""
-    code = _mlp_act(act)
-    S, D = w_out.shape
-    n_mid = s1.shape[0]
-    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
-    if not mlp_apply_supported(first, n_mid, D):
-        raise RuntimeError(f"mlp_apply: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
-    ops = (x, w_in, s1, s2, u, w_out) + tuple(t for t in (b_in, b_mid, b_out) if t is not None)
-    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
-        raise RuntimeError("mlp_apply: float32 CUDA tensors on one device only")
-    B = x.shape[0]
-    if (tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D) or tuple(s1.shape) != (n_mid, D)
-            or tuple(s2.shape) != (n_mid, D) or tuple(u.shape) != (n_mid, S + 1, D)
-            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)
-            or (b_out is not None and b_out.numel() != 1)):
-        raise RuntimeError("mlp_apply: operand shapes do not match")
-    x, w_in, s1, s2, u, w_out = (_aligned(t) for t in (x, w_in, s1, s2, u, w_out))
-    b_in, b_mid, b_out = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid, b_out))
+    code, _, _, S, B, _, args, keep = _mlp_operands("mlp_apply", mlp_apply_supported, act, x, w_in, b_in, s1, s2, u, 1, b_mid,
+                                                    mid_bias, w_out, b_out)
     y = torch.empty((S, B), dtype=torch.float32, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with _OnDevice(x.device):
         if act == "relu":
-            rc = lib().whvi_mlp_apply_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid, s1.data_ptr(),
-                                          s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias), w_out.data_ptr(), ptr(b_out),
-                                          S, B, D.bit_length() - 1, int(relu), _stream(x))
+            rc = lib().whvi_mlp_apply_f32(y.data_ptr(), *args, int(relu), _stream(x))
         else:
-            rc = lib().whvi_mlp_apply_act_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
-                                              s1.data_ptr(), s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias),
-                                              w_out.data_ptr(), ptr(b_out), S, B, D.bit_length() - 1, code, int(relu), _stream(x))
+            rc = lib().whvi_mlp_apply_act_f32(y.data_ptr(), *args, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply")
     return y
-
-
-def mlp_fastfood_apply_supported(first: int, n_mid: int, d: int) -> bool:
-    """The rule of ``whvi_mlp_fastfood_apply_supported`` (include/whvi_hip.h) without the library: first-layer kind 1 / 4 / 8,
-    1 .. 4 fastfood square layers, D = 64 .. 2048 a power of two, and one sample's operands -- 4 D (K + 2 + 4 n_mid) bytes
-    (s1, s2, g_k and the bias per square layer) -- within 64 KiB of LDS."""
-    return (first in (MLP_FIRST_COLUMN, MLP_FIRST_K4, MLP_FIRST_K8) and 1 <= n_mid <= 4 and 64 <= d <= 2048
-            and (d & (d - 1)) == 0 and 4 * d * (first + 2 + 4 * n_mid) <= 65536)
 
 
 def mlp_fastfood_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor, g: torch.Tensor, b_mid,
@@ -804,38 +824,13 @@ def mlp_fastfood_apply(x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tens
     see whvi_mlp_fastfood_apply_f32 in include/whvi_hip.h.  x, w_in, b_in, w_out, b_out, ``act`` and ``act_bits`` as
     ``mlp_apply``; s1, s2 (n_mid, D); g (n_mid, S, D), every sample's g_k; b_mid (n_mid, D) or None (``mid_bias`` bit m:
     square layer m has a bias)."""
-    code = _mlp_act(act)
-    S, D = w_out.shape
-    n_mid = s1.shape[0]
-    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
-    if not mlp_fastfood_apply_supported(first, n_mid, D):
-        raise RuntimeError(f"mlp_fastfood_apply: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
-    ops = (x, w_in, s1, s2, g, w_out) + tuple(t for t in (b_in, b_mid, b_out) if t is not None)
-    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
-        raise RuntimeError("mlp_fastfood_apply: float32 CUDA tensors on one device only")
-    B = x.shape[0]
-    if (tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D) or tuple(s1.shape) != (n_mid, D)
-            or tuple(s2.shape) != (n_mid, D) or tuple(g.shape) != (n_mid, S, D)
-            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)
-            or (b_out is not None and b_out.numel() != 1)):
-        raise RuntimeError("mlp_fastfood_apply: operand shapes do not match")
-    x, w_in, s1, s2, g, w_out = (_aligned(t) for t in (x, w_in, s1, s2, g, w_out))
-    b_in, b_mid, b_out = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid, b_out))
+    code, _, _, S, B, _, args, keep = _mlp_operands("mlp_fastfood_apply", mlp_fastfood_apply_supported, act, x, w_in, b_in, s1, s2,
+                                                    g, 0, b_mid, mid_bias, w_out, b_out)
     y = torch.empty((S, B), dtype=torch.float32, device=x.device)
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     with _OnDevice(x.device):
-        rc = lib().whvi_mlp_fastfood_apply_f32(y.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
-                                               s1.data_ptr(), s2.data_ptr(), g.data_ptr(), ptr(b_mid), int(mid_bias),
-                                               w_out.data_ptr(), ptr(b_out), S, B, D.bit_length() - 1, code, int(act_bits),
-                                               _stream(x))
+        rc = lib().whvi_mlp_fastfood_apply_f32(y.data_ptr(), *args, code, int(act_bits), _stream(x))
     _check(rc, "whvi_mlp_fastfood_apply")
     return y
-
-
-def mlp_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
-    """The rule of ``whvi_mlp_apply_bwd_supported`` (include/whvi_hip.h) without the library: ``mlp_apply_supported`` with at
-    most 2 square layers and D <= 1024."""
-    return mlp_apply_supported(first, n_mid, d) and n_mid <= 2 and d <= 1024
 
 
 def mlp_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor,
@@ -845,49 +840,26 @@ def mlp_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1
     "tanh"): ``(grad_w_in, grad_w_mid (n_mid, S, D), grad_w_out (S, D), grad_b ((1 + n_mid) D + 1: b_in, b_mid rows, b_out),
     grad_x (S, B, K) or None)`` from ``g`` = dL/dy (S, B) and the forward's operands (same shapes and ``relu`` / ``act`` as
     ``mlp_apply``)."""
-    code = _mlp_act(act)
-    S, D = w_out.shape
-    n_mid = s1.shape[0]
-    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
-    if not mlp_apply_bwd_supported(first, n_mid, D):
-        raise RuntimeError(f"mlp_apply_bwd: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
-    B = x.shape[0]
-    ops = (g, x, w_in, s1, s2, u, w_out) + tuple(t for t in (b_in, b_mid) if t is not None)
-    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
-        raise RuntimeError("mlp_apply_bwd: float32 CUDA tensors on one device only")
-    if (tuple(g.shape) != (S, B) or tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D)
-            or tuple(s1.shape) != (n_mid, D) or tuple(s2.shape) != (n_mid, D) or tuple(u.shape) != (n_mid, S + 1, D)
-            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)):
-        raise RuntimeError("mlp_apply_bwd: operand shapes do not match")
-    g, x, w_in, s1, s2, u, w_out = (_aligned(t) for t in (g, x, w_in, s1, s2, u, w_out))
-    b_in, b_mid = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid))
+    code, first, n_mid, S, B, D, args, keep = _mlp_operands("mlp_apply_bwd", mlp_apply_bwd_supported, act, x, w_in, b_in, s1, s2,
+                                                            u, 1, b_mid, mid_bias, w_out, g=g)
     dev = x.device
     grad_w_in = torch.empty(tuple(w_in.shape), dtype=torch.float32, device=dev)
     grad_w_mid = torch.empty((n_mid, S, D), dtype=torch.float32, device=dev)
     grad_w_out = torch.empty((S, D), dtype=torch.float32, device=dev)
     grad_b = torch.empty(((1 + n_mid) * D + 1,), dtype=torch.float32, device=dev)
     grad_x = torch.empty((S, B, first), dtype=torch.float32, device=dev) if need_grad_x else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     L = lib()
-    log2d = D.bit_length() - 1
     with _OnDevice(dev):
-        n = int(L.whvi_mlp_apply_bwd_workspace(S, B, first, n_mid, log2d))
+        n = int(L.whvi_mlp_apply_bwd_workspace(S, B, first, n_mid, D.bit_length() - 1))
         work = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
-        args = (grad_w_in.data_ptr(), grad_w_mid.data_ptr(), grad_w_out.data_ptr(), grad_b.data_ptr(), ptr(grad_x),
-                work.data_ptr(), n, g.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid, s1.data_ptr(),
-                s2.data_ptr(), u.data_ptr(), ptr(b_mid), int(mid_bias), w_out.data_ptr(), S, B, log2d)
+        outs = (grad_w_in.data_ptr(), grad_w_mid.data_ptr(), grad_w_out.data_ptr(), grad_b.data_ptr(), _ptr(grad_x),
+                work.data_ptr(), n)
         if act == "relu":
-            rc = L.whvi_mlp_apply_bwd_f32(*args, int(relu), _stream(x))
+            rc = L.whvi_mlp_apply_bwd_f32(*outs, *args, int(relu), _stream(x))
         else:
-            rc = L.whvi_mlp_apply_act_bwd_f32(*args, code, int(relu), _stream(x))
+            rc = L.whvi_mlp_apply_act_bwd_f32(*outs, *args, code, int(relu), _stream(x))
     _check(rc, "whvi_mlp_apply_bwd")
     return grad_w_in, grad_w_mid, grad_w_out, grad_b, grad_x
-
-
-def mlp_fastfood_apply_bwd_supported(first: int, n_mid: int, d: int) -> bool:
-    """The rule of ``whvi_mlp_fastfood_apply_bwd_supported`` (include/whvi_hip.h) without the library:
-    ``mlp_fastfood_apply_supported`` with at most 2 square layers and D <= 1024."""
-    return mlp_fastfood_apply_supported(first, n_mid, d) and n_mid <= 2 and d <= 1024
 
 
 def mlp_fastfood_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor, b_in, s1: torch.Tensor, s2: torch.Tensor,
@@ -897,22 +869,8 @@ def mlp_fastfood_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor,
     grad_s2 (n_mid, D), grad_g (n_mid, S, D), grad_w_out (S, D), grad_b ((1 + n_mid) D + 1: b_in, b_mid rows, b_out),
     grad_x (S, B, K) or None)`` from ``g`` = dL/dy (S, B) and the forward's operands (``gk`` is its ``g``; same shapes,
     ``act_bits`` and ``act`` as ``mlp_fastfood_apply``)."""
-    code = _mlp_act(act)
-    S, D = w_out.shape
-    n_mid = s1.shape[0]
-    first = MLP_FIRST_COLUMN if w_in.dim() == 2 else w_in.shape[2]
-    if not mlp_fastfood_apply_bwd_supported(first, n_mid, D):
-        raise RuntimeError(f"mlp_fastfood_apply_bwd: unsupported network (first layer {first}, {n_mid} square layers, D = {D})")
-    B = x.shape[0]
-    ops = (g, x, w_in, s1, s2, gk, w_out) + tuple(t for t in (b_in, b_mid) if t is not None)
-    if any(t.device != x.device or t.dtype != torch.float32 for t in ops) or x.device.type != "cuda":
-        raise RuntimeError("mlp_fastfood_apply_bwd: float32 CUDA tensors on one device only")
-    if (tuple(g.shape) != (S, B) or tuple(x.shape) != (B, first) or tuple(w_in.shape[:2]) != (S, D)
-            or tuple(s1.shape) != (n_mid, D) or tuple(s2.shape) != (n_mid, D) or tuple(gk.shape) != (n_mid, S, D)
-            or (b_mid is not None and b_mid.numel() != n_mid * D) or (b_in is not None and b_in.numel() != D)):
-        raise RuntimeError("mlp_fastfood_apply_bwd: operand shapes do not match")
-    g, x, w_in, s1, s2, gk, w_out = (_aligned(t) for t in (g, x, w_in, s1, s2, gk, w_out))
-    b_in, b_mid = (None if t is None else _aligned(t.reshape(-1)) for t in (b_in, b_mid))
+    code, first, n_mid, S, B, D, args, keep = _mlp_operands("mlp_fastfood_apply_bwd", mlp_fastfood_apply_bwd_supported, act, x,
+                                                            w_in, b_in, s1, s2, gk, 0, b_mid, mid_bias, w_out, g=g)
     dev = x.device
     grad_w_in = torch.empty(tuple(w_in.shape), dtype=torch.float32, device=dev)
     grad_s1 = torch.empty((n_mid, D), dtype=torch.float32, device=dev)
@@ -921,17 +879,13 @@ def mlp_fastfood_apply_bwd(g: torch.Tensor, x: torch.Tensor, w_in: torch.Tensor,
     grad_w_out = torch.empty((S, D), dtype=torch.float32, device=dev)
     grad_b = torch.empty(((1 + n_mid) * D + 1,), dtype=torch.float32, device=dev)
     grad_x = torch.empty((S, B, first), dtype=torch.float32, device=dev) if need_grad_x else None
-    ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
     L = lib()
-    log2d = D.bit_length() - 1
     with _OnDevice(dev):
-        n = int(L.whvi_mlp_fastfood_apply_bwd_workspace(S, B, first, n_mid, log2d))
+        n = int(L.whvi_mlp_fastfood_apply_bwd_workspace(S, B, first, n_mid, D.bit_length() - 1))
         work = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
         rc = L.whvi_mlp_fastfood_apply_bwd_f32(grad_w_in.data_ptr(), grad_s1.data_ptr(), grad_s2.data_ptr(), grad_g.data_ptr(),
-                                               grad_w_out.data_ptr(), grad_b.data_ptr(), ptr(grad_x), work.data_ptr(), n,
-                                               g.data_ptr(), x.data_ptr(), first, w_in.data_ptr(), ptr(b_in), n_mid,
-                                               s1.data_ptr(), s2.data_ptr(), gk.data_ptr(), ptr(b_mid), int(mid_bias),
-                                               w_out.data_ptr(), S, B, log2d, code, int(act_bits), _stream(x))
+                                               grad_w_out.data_ptr(), grad_b.data_ptr(), _ptr(grad_x), work.data_ptr(), n,
+                                               *args, code, int(act_bits), _stream(x))
     _check(rc, "whvi_mlp_fastfood_apply_bwd")
     return grad_w_in, grad_s1, grad_s2, grad_g, grad_w_out, grad_b, grad_x
 

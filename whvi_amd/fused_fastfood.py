@@ -20,18 +20,16 @@ on every run).  They differ from the batched route's gradients only by summation
 gradient w.r.t. every sample's ``g_k`` goes back through ``_mc_operands`` to ``g_mu`` and ``g_rho`` by autograd.  There is no
 double backward.
 
-``match(net)`` is the structural check (no device needed), ``plan(net, x, n_samples[, training])`` adds the checks of one call,
-``run`` makes the pass.  Both return a human-readable reason instead of a plan when the network or the call is not covered; the
-caller then takes the batched route.  The predictive plan (``training=False``) refuses a call that wants an autograd graph;
-the training plan (``training=True``) takes exactly those, within ``whvi_mlp_fastfood_apply_bwd_f32``'s narrower range."""
+``match``, ``plan`` and ``run`` are ``fused_mlp``'s in form and meaning, on the same shared code (``whvi_amd._fused_net``); the
+training plan's range is ``whvi_mlp_fastfood_apply_bwd_f32``'s.  Here are the fastfood layers' checks and their operands' layout."""
 from typing import List, NamedTuple, Union
 
 import torch
 import torch.nn as nn
 
-from whvi_amd import _hip
+from whvi_amd import _fused_net, _hip
+from whvi_amd._fused_net import _act_bits, _first_layer, _output_layer, _scan
 from whvi_amd.fastfood import WHVIFastfoodMatrix
-from whvi_amd.fused_mlp import _act_bits, _first_layer, _output_layer, _scan
 from whvi_amd.weights import WHVIColumnMatrix, WHVISquarePow2Matrix, WHVIStackedMatrix
 
 __all__ = ["Plan", "FastfoodMLPApplyFunction", "match", "plan", "run"]
@@ -87,30 +85,14 @@ def match(net) -> Union[Plan, str]:
     return Plan(first, kind, n_in, list(mids), last, layers, D, act or "relu", _act_bits(act_after))
 
 
+_KIND = _fused_net.Kind("fused fastfood pass", "fastfood layers is outside whvi_mlp_fastfood_apply_bwd's range",
+                        _hip.mlp_fastfood_apply_bwd_supported)
+
+
 def plan(net, x: torch.Tensor, n_samples: int, training: bool = False) -> Union[Plan, str]:
-    """``match(net)`` plus the checks of this call: float32 CUDA input and parameters on x's device, sizes, and no autograd
-    graph wanted (grad mode off, or neither x nor any parameter of the pass requires grad).  ``training=True``: the plan of the
-    trainable pass instead -- the same checks, but a graph must be wanted and the network must lie in the backward's range
-    (``_hip.mlp_fastfood_apply_bwd_supported``)."""
-    p = match(net)
-    if isinstance(p, str):
-        return p
-    if x.device.type != "cuda" or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != p.n_in:
-        return f"input: needs a float32 CUDA (batch, {p.n_in}) tensor"
-    params = [t for m in p.layers for t in m.parameters()]
-    if any(t.device != x.device or t.dtype != torch.float32 for t in params):
-        return "parameters: float32 on the input's device only"
-    S, B = int(n_samples), x.shape[0]
-    if S < 1 or S * B >= 2 ** 32:
-        return f"{S} samples x {B} rows: outside 1 .. 2^32 - 1 rows"
-    wanted = torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in params))
-    if not training:
-        return "an autograd graph is wanted (the fused fastfood pass has no backward)" if wanted else p
-    if not wanted:
-        return "no autograd graph is wanted (the training pass is for passes that need one)"
-    if not _hip.mlp_fastfood_apply_bwd_supported(p.kind, len(p.mids), p.D):
-        return f"hidden width {p.D} with {len(p.mids)} fastfood layers is outside whvi_mlp_fastfood_apply_bwd's range"
-    return p
+    """``match(net)`` plus the checks of this call, ``fused_mlp.plan``'s (``_fused_net.check_call``); the training plan's range is
+    ``_hip.mlp_fastfood_apply_bwd_supported``."""
+    return _fused_net.check_call(_KIND, match(net), x, n_samples, training)
 
 
 class FastfoodMLPApplyFunction(torch.autograd.Function):
@@ -128,56 +110,31 @@ class FastfoodMLPApplyFunction(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy):
-        if torch.is_grad_enabled():
-            raise RuntimeError("FastfoodMLPApplyFunction: the fused training pass has no double backward -- call backward() "
-                               "without create_graph=True, or turn WHVINetwork.set_fused_training off for this pass")
+        _fused_net.refuse_double_backward("FastfoodMLPApplyFunction")
         x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out = ctx.saved_tensors
-        need = ctx.needs_input_grad
         gw_in, gs1, gs2, gg, gw_out, gb, gx = _hip.mlp_fastfood_apply_bwd(gy, x, w_in, b_in, s1, s2, g, b_mid, w_out,
                                                                           mid_bias=ctx.mid_bias, act_bits=ctx.act_bits,
-                                                                          need_grad_x=need[0], act=ctx.act)
+                                                                          need_grad_x=ctx.needs_input_grad[0], act=ctx.act)
         n_mid, S, D = gg.shape
         grad_x = gx.sum(dim=0) if gx is not None else None
-        grad_b_in = gb[:D].view(b_in.shape) if b_in is not None else None
-        grad_b_mid = gb[D:(1 + n_mid) * D].view(b_mid.shape) if b_mid is not None else None
-        grad_b_out = gb[(1 + n_mid) * D:].view(b_out.shape) if b_out is not None else None
+        grad_b_in, grad_b_mid, grad_b_out = _fused_net.bias_grads(gb, n_mid, D, b_in, b_mid, b_out)
         return grad_x, gw_in, grad_b_in, gs1, gs2, gg, grad_b_mid, gw_out, grad_b_out, None, None, None
 
 
-def _bias(w):
-    return None if w.bias is None else w.bias.reshape(-1)
+def _apply(x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out, mid_bias, act_bits, act):
+    return _hip.mlp_fastfood_apply(x, w_in, b_in, s1, s2, g, b_mid, w_out, b_out, mid_bias=mid_bias, act_bits=act_bits, act=act)
+
+
+def _stack(mids, drawn):
+    """``s1, s2`` (n_mid, D) and ``g`` (n_mid, S, D) of the fastfood layers (copies at every depth)."""
+    return torch.stack([w.s1 for w in mids]), torch.stack([w.s2 for w in mids]), torch.stack(drawn)
 
 
 def run(net, p: Plan, x: torch.Tensor, n_samples: int, training: bool = False) -> torch.Tensor:
-    """The pass: each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them), then ONE launch
-    (``training``: through ``FastfoodMLPApplyFunction``, for a plan of ``plan(..., training=True)``).
+    """The pass (``_fused_net.launch``): each layer's draws in module order (``_mc_operands``, as ``forward_mc`` makes them),
+    then ONE launch (``training``: through ``FastfoodMLPApplyFunction``, for a plan of ``plan(..., training=True)``).
     Returns ``(batch, 1, S)`` in forward_batched's layout; sets ``net._pass_kl`` as the batched route does -- to None, because
     fastfood layers report no in-pass KL."""
-    S = int(n_samples)
-    first = p.first
-    w_in, _ = first._mc_operands(S)                                 # (S, D, K) or (S, D)
-    if p.kind == _hip.MLP_FIRST_COLUMN:
-        xin = x
-    else:
-        xin = torch.zeros((x.shape[0], first.D_in), device=x.device)   # forward_mc's x_padded
-        xin[:, :first.n_in] = x
-    gs = [w._mc_operands(S) for w in p.mids]                        # (S, D) each
-    w_out, _ = p.last._mc_operands(S)                               # (S, D)
-    for m in p.layers:
-        m._mc_kl = None
-        m.weight_submodule._mc_kl = None
-    s1 = torch.stack([w.s1 for w in p.mids])
-    s2 = torch.stack([w.s2 for w in p.mids])
-    g = torch.stack(gs)
-    mid_bias = sum(1 << j for j, w in enumerate(p.mids) if w.bias is not None)
-    b_mid = None
-    if mid_bias:
-        b_mid = torch.stack([w.bias.reshape(-1) if w.bias is not None else torch.zeros_like(w.s1) for w in p.mids])
-    if training:
-        y = FastfoodMLPApplyFunction.apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias, p.act_bits,
-                                           p.act)
-    else:
-        y = _hip.mlp_fastfood_apply(xin, w_in, _bias(first), s1, s2, g, b_mid, w_out, _bias(p.last), mid_bias=mid_bias,
-                                    act_bits=p.act_bits, act=p.act)
+    y, _, _ = _fused_net.launch(p, x, n_samples, _stack, FastfoodMLPApplyFunction.apply if training else _apply)
     net._pass_kl = None
-    return y.unsqueeze(-1).permute(1, 2, 0)
+    return y

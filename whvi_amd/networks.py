@@ -90,31 +90,29 @@ class WHVINetwork(nn.Module, WHVI):
         return self
 
     def set_fused_inference(self, on: bool = True):
-        """Opt in to the one-launch predictive pass (``whvi_amd.fused_mlp``, ``whvi_mlp_apply_f32``) for networks of the
-        reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4 ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, with or without an
-        activation at each boundary: ``nn.ReLU``, ``nn.Sigmoid`` or ``nn.Tanh``, one kind per network (the smooth ones through
-        ``whvi_mlp_apply_act_f32``, with ATen's float formulas); n_in <= 8.  ``forward_batched`` then makes the same draws in
-        the same order and computes the same values without materialising the ``(S, batch, D)`` activations (bit for bit for
-        ReLU networks; DESIGN.md 5.3e for the smooth ones), whenever no autograd graph is wanted (grad mode off, or nothing of
-        the pass requires grad) -- otherwise, and for other networks, it takes the batched route as before (a pass that wants
-        a graph takes the fused route only with ``set_fused_training``).  Networks whose square layers are all fastfood layers
-        (``WHVILinear(D, D, mode="fastfood")``, 1 .. 4 of them) take ``whvi_amd.fused_fastfood`` under the same flag and rules
-        (bit for bit for every activation; their trainable form is ``set_fused_training``'s too).  ``eval_model`` evaluates under ``torch.no_grad()`` while the
-        flag is on."""
+        """Opt in to the one-launch predictive pass for networks of the reference's shape -- ``WHVILinear(n_in, D)``, 1 .. 4
+        ``WHVILinear(D, D)``, ``WHVILinear(D, 1)``, with or without an activation at each boundary: ``nn.ReLU``, ``nn.Sigmoid``
+        or ``nn.Tanh``, one kind per network; n_in <= 8.  The square layers are all diagonal (``whvi_amd.fused_mlp``:
+        ``whvi_mlp_apply_f32``, ``whvi_mlp_apply_act_f32`` for sigmoid and tanh, with ATen's float formulas) or all
+        ``mode="fastfood"`` (``whvi_amd.fused_fastfood``: ``whvi_mlp_fastfood_apply_f32``); both kinds share their plan checks
+        and operand gathering (``whvi_amd._fused_net``).  ``forward_batched`` then makes the same draws in the same order and
+        computes the same values without materialising the ``(S, batch, D)`` activations (bit for bit; DESIGN.md 5.3e for the
+        smooth diagonal networks), whenever the call wants no autograd graph (grad mode off, or nothing of the pass requires
+        grad) -- otherwise, and for other networks, it takes the batched route as before (a pass that wants a graph takes the
+        fused route only with ``set_fused_training``).  ``eval_model`` evaluates under ``torch.no_grad()`` while the flag is on."""
         self.fused_inference = bool(on)
         return self
 
     def set_fused_training(self, on: bool = True):
-        """Opt in to the trainable one-launch pass (``whvi_amd.fused_mlp.MLPApplyFunction``: ``whvi_mlp_apply_f32`` forward,
-        ``whvi_mlp_apply_bwd_f32`` backward; ``whvi_mlp_apply_act_f32`` / ``whvi_mlp_apply_act_bwd_f32`` for sigmoid and tanh
-        networks, whose backward applies torch's formulas to the recomputed activation outputs) for the networks
-        ``set_fused_inference`` covers, with at most 2 square layers and D <= 1024.  A ``forward_batched`` call that wants an
-        autograd graph then makes the same draws, returns the forward values ``set_fused_inference`` returns and saves no
-        ``(S, batch, D)`` activation; its gradients differ from the batched route's only by summation order, and are the same on
-        every run.  Networks whose square layers are all fastfood layers take ``whvi_amd.fused_fastfood``'s trainable pass under
-        the same flag (``whvi_mlp_fastfood_apply_f32`` forward, ``whvi_mlp_fastfood_apply_bwd_f32`` backward; at most 2 fastfood
-        layers, D <= 1024).  No double backward (``create_graph=True`` raises).  Every other call takes the route it takes without this
-        flag; the two flags are independent."""
+        """Opt in to the trainable one-launch pass for the networks ``set_fused_inference`` covers, with at most 2 square layers
+        and D <= 1024: ``whvi_amd.fused_mlp.MLPApplyFunction`` (``whvi_mlp_apply_f32`` forward, ``whvi_mlp_apply_bwd_f32``
+        backward; ``whvi_mlp_apply_act_f32`` / ``whvi_mlp_apply_act_bwd_f32`` for sigmoid and tanh networks, whose backward
+        applies torch's formulas to the recomputed activation outputs) or, for fastfood square layers,
+        ``whvi_amd.fused_fastfood.FastfoodMLPApplyFunction`` (``whvi_mlp_fastfood_apply_f32`` / ``whvi_mlp_fastfood_apply_bwd_f32``).
+        A ``forward_batched`` call that wants an autograd graph then makes the same draws, returns the forward values
+        ``set_fused_inference`` returns and saves no ``(S, batch, D)`` activation; its gradients differ from the batched route's
+        only by summation order, and are the same on every run.  No double backward (``create_graph=True`` raises).  Every other
+        call takes the route it takes without this flag; the two flags are independent."""
         self.fused_training = bool(on)
         return self
 
@@ -141,24 +139,15 @@ class WHVINetwork(nn.Module, WHVI):
         """All Monte-Carlo samples in one pass.  Activations carry a leading sample
         axis ``(S, batch, features)`` from the first WHVI layer on; deterministic modules broadcast
         over it.  Same output layout as the loop: ``(batch, out_dim, n_samples)``."""
-        if self.fused_inference:
-            from whvi_amd import fused_mlp
-            plan = fused_mlp.plan(self, x, n_samples)
-            if not isinstance(plan, str):
-                return fused_mlp.run(self, plan, x, n_samples)
-            from whvi_amd import fused_fastfood          # networks with fastfood square layers (whvi_mlp_fastfood_apply_f32)
-            plan = fused_fastfood.plan(self, x, n_samples)
-            if not isinstance(plan, str):
-                return fused_fastfood.run(self, plan, x, n_samples)
-        if self.fused_training and torch.is_grad_enabled():
-            from whvi_amd import fused_mlp
-            plan = fused_mlp.plan(self, x, n_samples, training=True)
-            if not isinstance(plan, str):
-                return fused_mlp.run(self, plan, x, n_samples, training=True)
-            from whvi_amd import fused_fastfood          # fastfood square layers (whvi_mlp_fastfood_apply_bwd_f32)
-            plan = fused_fastfood.plan(self, x, n_samples, training=True)
-            if not isinstance(plan, str):
-                return fused_fastfood.run(self, plan, x, n_samples, training=True)
+        # the opt-in one-launch passes: the predictive one first, then the trainable one; a refused plan (a reason string) falls
+        # through to the next candidate and finally to the batched route below
+        for on, training in ((self.fused_inference, False), (self.fused_training and torch.is_grad_enabled(), True)):
+            if on:
+                from whvi_amd import fused_fastfood, fused_mlp
+                for fused in (fused_mlp, fused_fastfood):        # diagonal square layers, then fastfood ones
+                    plan = fused.plan(self, x, n_samples, training)
+                    if not isinstance(plan, str):
+                        return fused.run(self, plan, x, n_samples, training)
         h = x
         fused_kl, complete = None, True
         modules = list(self.sequential)
