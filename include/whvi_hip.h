@@ -245,6 +245,28 @@ int whvi_fused_shs_ex_bf16(void *dst, const void *src, const void *a, const void
                            int64_t sample_stride, int64_t group_rows, int32_t axis,
                            int32_t flags, void *stream);
 
+/* whvi_fused_shs_bwd_f32 on 16-bit ACTIVATION streams: grad_x, grad_y and x are IEEE half (_f16) or bfloat16 (_bf16); a, b, c,
+ * grad_a, grad_b, grad_c and the workspace stay FLOAT32.  The argument list, the flags (0 / WHVI_FUSED_SRC_SHARED), the layout
+ * and every check are those of whvi_fused_shs_bwd_f32, with the extents of grad_x, grad_y and x counted in 2-byte elements.
+ * whvi_fused_shs_bwd_supported and whvi_fused_shs_bwd_workspace serve the three entries unchanged: the grid and the slots do
+ * not depend on the storage type.
+ *   Rounding: every element of x and grad_y is converted to f32 exactly, the chain of whvi_fused_shs_bwd_f32 runs on those
+ *   values -- every multiply its own f32 rounding, f32 butterflies in the forward's order, fused multiply-adds into f32 sums --
+ *   and grad_x is rounded to the storage type ONCE (round to nearest even; a bf16 NaN stays a NaN) when it is stored.  Nothing
+ *   is rounded to 16 bits in between.  Hence grad_x is element for element whvi_fused_shs_ex_f16 / _bf16(grad_x, grad_y,
+ *   a := c, b, c := a, ...) (the sign of an exact zero is exempt, as for that entry), and the parameter gradients are the sums
+ *   whvi_fused_shs_bwd_f32 forms on the upcast operands: bit for bit from log2d = 9 up, where every column adds the same rows
+ *   in the same order; the same products in another lane order below.
+ *   HBM traffic: 6 * D bytes per row -- x and grad_y read once, grad_x written once (4 * D with grad_x = NULL or a shared x
+ *   that stays in cache) -- and no activation-sized temporary.
+ * whvi_last_kernel names whvi::fused_shs_bwd_kernel<__half, log2d, K, NT> / <__hip_bfloat16, log2d, K, NT>. */
+int     whvi_fused_shs_bwd_f16 (void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                                const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                                int64_t n_samples, int64_t sample_stride, int32_t log2d, int32_t flags, void *stream);
+int     whvi_fused_shs_bwd_bf16(void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                                const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                                int64_t n_samples, int64_t sample_stride, int32_t log2d, int32_t flags, void *stream);
+
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample
  * (src/weights.py:82-83,92), and kl_diag_normal(g_mu, g_sigma, 0, lambda) (src/weights.py:52-64,

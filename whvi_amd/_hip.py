@@ -123,8 +123,10 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_bwd_supported.argtypes = [i32]
     lib.whvi_fused_shs_bwd_workspace.restype = i64
     lib.whvi_fused_shs_bwd_workspace.argtypes = [i64, i64, i32]
-    lib.whvi_fused_shs_bwd_f32.restype = ctypes.c_int
-    lib.whvi_fused_shs_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+    for sfx in ("f32", "f16", "bf16"):                # (16-bit: grad_x, grad_y and x; everything else float32)
+        fn = getattr(lib, "whvi_fused_shs_bwd_" + sfx)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -375,26 +377,46 @@ def fused_shs_bwd_supported(dtype: torch.dtype, d: int) -> bool:
     return bool(lib().whvi_fused_shs_bwd_supported(d.bit_length() - 1))
 
 
+def fused_shs_bwd16_supported(dtype: torch.dtype, d: int) -> bool:
+    """Row lengths the one-launch backward covers on 16-bit activation streams (``whvi_fused_shs_bwd_f16 / _bf16``): float16 /
+    bfloat16, 64 <= D <= 4096 -- the float32 launch's range (``whvi_fused_shs_bwd_supported`` serves both widths)."""
+    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return bool(lib().whvi_fused_shs_bwd_supported(d.bit_length() - 1))
+
+
 def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int,
                   sample_stride: int, shared: bool = False, need_x: bool = True):
     """Backward of ``y = a * fwht(b_s * fwht(c * x))`` in one call (whvi_fused_shs_bwd_f32): ``(grad_x | None, grad_a (D),
     grad_b (S, D), grad_c (D))`` from ``grad_y`` ``(S * sample_stride, D)`` in (sample, row) order and the forward's operands.
     ``shared``: ``x`` is ``(sample_stride, D)``, read by every sample; ``grad_x`` still has ``S * sample_stride`` rows (the
     caller sums over samples).  ``need_x=False`` allocates and writes no ``grad_x``.  The workspace comes from torch's
-    allocator, sized by ``whvi_fused_shs_bwd_workspace``."""
+    allocator, sized by ``whvi_fused_shs_bwd_workspace``.
+
+    float16 / bfloat16 ``grad_y`` and ``x`` of one dtype with float32 ``a, b, c`` (whvi_fused_shs_bwd_f16 / _bf16): 6 * D bytes
+    per row, float32 arithmetic on the exactly-upcast values, ``grad_x`` in that dtype (rounded once, when it is stored: the
+    bits of ``fused_shs(grad_y, c, b, a)``) and float32 parameter gradients."""
     S, stride = int(n_samples), int(sample_stride)
     if grad_y.device.type != "cuda" or grad_y.dim() != 2:
         raise RuntimeError("fused_shs_bwd: grad_y must be a 2-D CUDA tensor")
     rows, d = grad_y.shape
-    _require_f32_on_one_device("fused_shs_bwd", grad_y.device, (grad_y, x, a, b, c))
-    if not fused_shs_bwd_supported(torch.float32, d):
-        raise RuntimeError(f"fused_shs_bwd: rows of {d} elements are outside the supported range 64 .. 4096")
+    act = grad_y.dtype
+    if act in _HALF_DTYPES:
+        if x.dtype != act or x.device != grad_y.device:
+            raise RuntimeError("fused_shs_bwd: grad_y and x must share one 16-bit dtype and device")
+        _require_f32_on_one_device("fused_shs_bwd (16-bit activations: a, b, c)", grad_y.device, (a, b, c))
+        if not fused_shs_bwd16_supported(act, d):
+            raise RuntimeError(f"fused_shs_bwd: {act} rows of {d} elements are outside the supported range 64 .. 4096")
+    else:
+        _require_f32_on_one_device("fused_shs_bwd", grad_y.device, (grad_y, x, a, b, c))
+        if not fused_shs_bwd_supported(torch.float32, d):
+            raise RuntimeError(f"fused_shs_bwd: rows of {d} elements are outside the supported range 64 .. 4096")
     if (rows != S * stride or tuple(x.shape) != ((stride if shared else rows), d) or a.numel() != d or c.numel() != d
             or b.numel() != S * d):
         raise RuntimeError("fused_shs_bwd: operand shapes do not match (rows must be n_samples * sample_stride)")
     grad_y, x, a, b, c = (_aligned(t) for t in (grad_y, x, a.reshape(-1), b.reshape(-1), c.reshape(-1)))
     dev = grad_y.device
-    grad_x = torch.empty((rows, d), dtype=torch.float32, device=dev) if need_x else None
+    grad_x = torch.empty((rows, d), dtype=act, device=dev) if need_x else None
     grad_a = torch.empty((d,), dtype=torch.float32, device=dev)
     grad_b = torch.empty((S, d), dtype=torch.float32, device=dev)
     grad_c = torch.empty((d,), dtype=torch.float32, device=dev)
@@ -407,10 +429,10 @@ def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: tor
         raise RuntimeError(f"whvi_fused_shs_bwd_workspace failed (code {n})")
     work = torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
     with _OnDevice(dev):
-        rc = L.whvi_fused_shs_bwd_f32(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(),
-                                      grad_c.data_ptr(), work.data_ptr(), grad_y.data_ptr(), x.data_ptr(), a.data_ptr(),
-                                      b.data_ptr(), c.data_ptr(), S, stride, log2d, FUSED_SRC_SHARED if shared else 0,
-                                      _stream(grad_y))
+        fn = getattr(L, "whvi_fused_shs_bwd_" + _DTYPE_SUFFIX[act])
+        rc = fn(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(), grad_c.data_ptr(),
+                work.data_ptr(), grad_y.data_ptr(), x.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), S, stride, log2d,
+                FUSED_SRC_SHARED if shared else 0, _stream(grad_y))
     _check(rc, "whvi_fused_shs_bwd")
     return grad_x, grad_a, grad_b, grad_c
 

@@ -1,6 +1,7 @@
 // whvi_amd/csrc/fused_bwd_f32.hip -- one-launch backward of the fused scale/FWHT/scale/FWHT/scale pipeline, float: the
 // instantiations of fused_shs_bwd_kernel (fused_bwd.hpp), the finishing launch and the ABI (include/whvi_hip.h:
-// whvi_fused_shs_bwd_supported, whvi_fused_shs_bwd_workspace, whvi_fused_shs_bwd_f32).  Built like fused_f32.hip:
+// whvi_fused_shs_bwd_supported, whvi_fused_shs_bwd_workspace, whvi_fused_shs_bwd_f32), and the argument checks and the
+// finishing launch that the 16-bit entries (fused_bwd_f16.hip, fused_bwd_bf16.hip) share.  Built like fused_f32.hip:
 // -ffp-contract=off -fno-slp-vectorize.
 #include "dispatch.hpp"
 #include "fused_bwd.hpp"
@@ -39,26 +40,11 @@ fused_shs_bwd_finish_kernel(float *__restrict__ ga, float *__restrict__ gb, floa
     *dst = acc;
 }
 
-template <int L>
-static void fused_bwd_launch_one(const FusedBwdArgs &a, hipStream_t st)
-{
-    constexpr int K = fused_bwd_k(L);
-    const dim3 grid((unsigned)(a.n_samples * a.geom.n_slabs));
-    const size_t lds = (size_t)fused_bwd_part_floats(L) * sizeof(float);
-    note_launch<float>("fused_shs_bwd_kernel", L, K, a.nt);
-#define WHVI_FUSED_BWD(NT)                                                                                              \
-    hipLaunchKernelGGL((fused_shs_bwd_kernel<float, L, K, NT>), grid, dim3(256), lds, st, (float *)a.work, (u32x4 *)a.grad_x, \
-                       (const u32x4 *)a.grad_y, (const u32x4 *)a.x, (const float *)a.a, (const float *)a.b, (const float *)a.c, \
-                       (uint32_t)a.sample_stride, (uint32_t)a.geom.slab_rows, (uint32_t)a.geom.n_slabs, a.x_shared ? 1u : 0u)
-    if (a.nt) WHVI_FUSED_BWD(true);
-    else WHVI_FUSED_BWD(false);
-#undef WHVI_FUSED_BWD
-}
-
-// Every argument check of whvi_fused_shs_bwd_f32, before any device call.  WHVI_OK with launch = false: nothing to launch.
-static int fused_bwd_check(FusedBwdArgs &r, bool &launch, void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
-                           const void *grad_y, const void *x, const void *a, const void *b, const void *c, int64_t S,
-                           int64_t stride, int32_t log2d, int32_t flags)
+// Every argument check of whvi_fused_shs_bwd_f32 / _f16 / _bf16 (act_bytes = 4 / 2 / 2: the element of x, grad_y and grad_x),
+// before any device call.  WHVI_OK with launch = false: nothing to launch.
+int fused_bwd_check(FusedBwdArgs &r, bool &launch, void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                    const void *grad_y, const void *x, const void *a, const void *b, const void *c, int64_t S, int64_t stride,
+                    int32_t log2d, int32_t flags, int64_t act_bytes)
 {
     g_err[0] = 0;
     launch = false;
@@ -82,23 +68,33 @@ static int fused_bwd_check(FusedBwdArgs &r, bool &launch, void *grad_x, void *gr
     if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_fused_shs_bwd: too many blocks%s", "");
     const int64_t D = (int64_t)1 << log2d, rows = S * stride;
     const bool shared = (flags & WHVI_FUSED_SRC_SHARED) != 0;
-    const struct { const void *p; int64_t n; } outs[] = {
-        {grad_x, rows * D}, {grad_a, D}, {grad_b, S * D}, {grad_c, D}, {work, S * geom.n_slabs * fused_bwd_part_floats(log2d)}};
-    const struct { const void *p; int64_t n; } ins[] = {
-        {grad_y, rows * D}, {x, (shared ? stride : rows) * D}, {a, D}, {b, S * D}, {c, D}};
+    const struct { const void *p; int64_t bytes; } outs[] = {
+        {grad_x, rows * D * act_bytes}, {grad_a, D * 4}, {grad_b, S * D * 4}, {grad_c, D * 4},
+        {work, S * geom.n_slabs * fused_bwd_part_floats(log2d) * 4}};
+    const struct { const void *p; int64_t bytes; } ins[] = {
+        {grad_y, rows * D * act_bytes}, {x, (shared ? stride : rows) * D * act_bytes}, {a, D * 4}, {b, S * D * 4}, {c, D * 4}};
     for (const auto &o : outs) {
         if (o.p == nullptr) continue;
         for (const auto &t : ins)
-            if (ranges_overlap(o.p, o.n * 4, t.p, t.n * 4))
+            if (ranges_overlap(o.p, o.bytes, t.p, t.bytes))
                 return fail(WHVI_ERR_OVERLAP, "whvi_fused_shs_bwd: grad_x, a parameter gradient or the workspace overlaps an "
                             "input%s", "");
     }
     r.grad_x = grad_x, r.work = work, r.grad_y = grad_y, r.x = x, r.a = a, r.b = b, r.c = c;
     r.n_samples = S, r.sample_stride = stride, r.log2d = log2d, r.x_shared = shared, r.geom = geom;
     // the streamed bytes: grad_y, x unless shared, grad_x unless skipped
-    r.nt = rows * D * 4 * (1 + (shared ? 0 : 1) + (grad_x != nullptr ? 1 : 0)) > NT_MIN_BYTES;
+    r.nt = rows * D * act_bytes * (1 + (shared ? 0 : 1) + (grad_x != nullptr ? 1 : 0)) > NT_MIN_BYTES;
     launch = true;
     return WHVI_OK;
+}
+
+int fused_bwd_finish(const FusedBwdArgs &r, void *grad_a, void *grad_b, void *grad_c, hipStream_t st)
+{
+    const int64_t total = (r.n_samples + 2) << r.log2d;
+    hipLaunchKernelGGL(fused_shs_bwd_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)grad_a,
+                       (float *)grad_b, (float *)grad_c, (const float *)r.work, (uint32_t)r.n_samples, (uint32_t)r.geom.n_slabs,
+                       (uint32_t)r.log2d);
+    return after_launch("fused_shs_bwd (finish)");
 }
 
 }  // namespace whvi
@@ -119,26 +115,6 @@ WHVI_EXPORT int whvi_fused_shs_bwd_f32(void *grad_x, void *grad_a, void *grad_b,
                                        const void *x, const void *a, const void *b, const void *c, int64_t n_samples,
                                        int64_t sample_stride, int32_t log2d, int32_t flags, void *stream)
 {
-    FusedBwdArgs r;
-    bool launch = false;
-    int rc = fused_bwd_check(r, launch, grad_x, grad_a, grad_b, grad_c, work, grad_y, x, a, b, c, n_samples, sample_stride, log2d,
-                             flags);
-    if (rc != WHVI_OK || !launch) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    switch (log2d) {
-    case 6: fused_bwd_launch_one<6>(r, st); break;
-    case 7: fused_bwd_launch_one<7>(r, st); break;
-    case 8: fused_bwd_launch_one<8>(r, st); break;
-    case 9: fused_bwd_launch_one<9>(r, st); break;
-    case 10: fused_bwd_launch_one<10>(r, st); break;
-    case 11: fused_bwd_launch_one<11>(r, st); break;
-    default: fused_bwd_launch_one<12>(r, st); break;
-    }
-    rc = after_launch("fused_shs_bwd");
-    if (rc != WHVI_OK) return rc;
-    const int64_t total = (n_samples + 2) << log2d;
-    hipLaunchKernelGGL(fused_shs_bwd_finish_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (float *)grad_a,
-                       (float *)grad_b, (float *)grad_c, (const float *)work, (uint32_t)n_samples, (uint32_t)r.geom.n_slabs,
-                       (uint32_t)log2d);
-    return after_launch("fused_shs_bwd (finish)");
+    return fused_bwd_run<float>(grad_x, grad_a, grad_b, grad_c, work, grad_y, x, a, b, c, n_samples, sample_stride, log2d, flags,
+                                stream);
 }

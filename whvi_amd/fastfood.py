@@ -19,7 +19,9 @@ Parity: bit-exact against `oracle.pipeline(axis="col")` (compositions of the ref
 16-bit activations (opt-in, ``WHVIFastfoodMatrix.keep_half``): a float16 / bfloat16 CUDA input is by default promoted to
 float32 by the first multiply and comes back as float32 through separate launches.  With ``keep_half = True`` the forward is
 ONE launch of ``whvi_fused_shs_ex_f16 / _bf16`` -- float32 parameters, float32 arithmetic, one rounding when the row is
-stored, 2 bytes read + 2 written per element -- and returns the input's dtype.
+stored, 2 bytes read + 2 written per element -- and returns the input's dtype.  With ``fused_backward = True`` as well, a
+backward that wants a parameter gradient is ONE launch of ``whvi_fused_shs_bwd_f16 / _bf16`` (6 bytes per element, float32
+sums, ``grad_x`` rounded once) instead of two float32 upcasts and the float32 chain; both flags default to False.
 """
 import torch
 import torch.nn as nn
@@ -101,7 +103,15 @@ class FastfoodFunction(torch.autograd.Function):
     wanting a gradient): the backward is ONE launch of ``whvi_fused_shs_bwd_f32`` -- ``x`` and ``grad_y`` read once, ``grad_x``
     written once, no activation-sized temporary -- plus the sum over samples for a shared ``x``.  ``grad_x`` has the bits of
     the chain's; the parameter gradients are the same sums in another order.  Everything else -- host tensors,
-    other dtypes or sizes, ``grad_x`` alone -- runs the code below unchanged."""
+    other dtypes or sizes, ``grad_x`` alone -- runs the code below unchanged.
+
+    ``keep_half`` AND ``fused_backward`` (the ``keep_half`` conditions, float32 ``a, b, c`` on ``x``'s device, 64 <= D <= 4096,
+    rows == n_samples * sample_stride, a parameter wanting a gradient): the backward is ONE launch of
+    ``whvi_fused_shs_bwd_f16 / _bf16`` -- 6 * D bytes per row instead of the two upcasts and the float32 chain, no float32 copy
+    of ``x`` or ``grad_y`` and no temporary but ``grad_x``.  ``grad_x`` is the 16-bit launch's (float32
+    arithmetic, rounded once), the parameter gradients are float32.  A shared ``x`` takes the launch only when it wants no
+    gradient: the per-sample gradients would each be rounded to 16 bits before they are added, where the chain rounds their
+    float32 sum once, so that case keeps the chain."""
 
     @staticmethod
     def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False):
@@ -125,6 +135,17 @@ class FastfoodFunction(torch.autograd.Function):
         if ctx.keep_half:
             if need_x and not (need_a or need_b or need_c or ctx.shared):
                 return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None, None, None, None, None, None
+            if (ctx.fused_backward and (need_a or need_b or need_c) and not (ctx.shared and need_x)
+                    and grad_y.dtype == x.dtype and grad_y.device == x.device
+                    and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
+                    and grad_y.size(0) == S * stride):
+                from whvi_amd import _hip
+                if _hip.fused_shs_bwd16_supported(x.dtype, x.size(1)):
+                    # ONE 16-bit launch: no float32 copy of x or grad_y, the sums in float32 (a shared x wants no gradient here)
+                    grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
+                                                                        need_x=need_x)
+                    return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
+                            grad_c if need_c else None, None, None, None, None, None)
             x, grad_y = x.float(), grad_y.float()
         if (ctx.fused_backward and not ctx.keep_half and (need_a or need_b or need_c) and x.dtype == torch.float32 and grad_y.dtype == torch.float32
                 and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
@@ -173,7 +194,7 @@ class WHVIFastfoodMatrix(nn.Module):
     """Square (D, D) WHVI layer in fastfood mode (see the module docstring): parameters ``s1, s2, g_mu, g_rho``
     (+ optional ``bias``) as in ``WHVISquarePow2Matrix``; ``forward(x)`` draws one eps, ``forward_mc(x, S)`` draws S
     and runs all samples in one launch."""
-    fused_backward = False    # float32 CUDA activations, 64 <= D <= 4096: True = the backward is one launch (FastfoodFunction); False: the chain
+    fused_backward = False    # float32 CUDA activations (16-bit ones with keep_half), 64 <= D <= 4096: True = the backward is one launch (FastfoodFunction); False: the chain
     keep_half = False         # float16 / bfloat16 CUDA activations: True = one 16-bit launch, output in the input's dtype (False: promoted to float32)
 
     def __init__(self, D, lambda_=1e-5, bias=False):
