@@ -267,6 +267,31 @@ int     whvi_fused_shs_bwd_bf16(void *grad_x, void *grad_a, void *grad_b, void *
                                 const void *grad_y, const void *x, const void *a, const void *b, const void *c,
                                 int64_t n_samples, int64_t sample_stride, int32_t log2d, int32_t flags, void *stream);
 
+/* The rectangular fastfood layer: n_blocks (J) independent square operators applied to the SAME rows, their outputs written
+ * side by side -- the paper's stacking of square blocks (src/weights.py: WHVIStackedMatrix.setup_dimensions) -- in ONE launch.
+ * float32.  Rows are in (sample, row) order: n_samples * sample_stride rows, sample s holds rows [s * sample_stride,
+ * (s + 1) * sample_stride).
+ *     dst[r, j * D + n] = a[j, n] * H(b[j, s, :] (.) H(c[j, :] (.) src_row))[n]
+ *   dst  : (n_samples * sample_stride, n_blocks * D).
+ *   src  : (n_samples * sample_stride, D), or with flags = WHVI_FUSED_SRC_SHARED (sample_stride, D): row r reads
+ *          src[r % sample_stride].
+ *   a, c : (n_blocks, D);  b : (n_blocks, n_samples, D).
+ * Every multiply is its own rounding and the transforms are the ones whvi_fused_shs_f32 runs: block j of dst is, element for
+ * element, whvi_fused_shs_f32(src, a[j], b[j], c[j], axis = WHVI_AXIS_COL) -- non-finite inputs included, the sign of an exact
+ * zero exempt as it is for that entry.  A row is read once and n_blocks segments are written: (1 + n_blocks) * D elements per
+ * row, where n_blocks launches and a concatenation move about 4 * n_blocks * D.
+ * Supported: 6 <= log2d <= 11, n_blocks >= 1 and 12 * D * n_blocks <= 65536 (every block of the launch stages all n_blocks
+ * triples a_j, b_{j,s}, c_j in LDS) -- whvi_fused_shs_stacked_supported(log2d, n_blocks) returns 1 exactly then (no device
+ * needed), the call WHVI_ERR_SIZE otherwise, as it does when n_samples * sample_stride >= 2^32.  flags other than 0 /
+ * WHVI_FUSED_SRC_SHARED, a null pointer, a negative size: WHVI_ERR_ARG; a pointer that is not 16-byte aligned: WHVI_ERR_ALIGN;
+ * dst overlapping any input: WHVI_ERR_OVERLAP.  n_samples * sample_stride == 0 returns WHVI_OK without a launch.  Every
+ * argument check runs before any device call.  No atomics, no allocation, no synchronisation: capture-safe.  whvi_last_kernel
+ * names whvi::fused_shs_stacked_kernel<float, log2d, K, NT>. */
+int whvi_fused_shs_stacked_supported(int32_t log2d, int64_t n_blocks);
+int whvi_fused_shs_stacked_f32(void *dst, const void *src, const void *a, const void *b, const void *c,
+                               int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                               int32_t log2d, int32_t flags, void *stream);
+
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample
  * (src/weights.py:82-83,92), and kl_diag_normal(g_mu, g_sigma, 0, lambda) (src/weights.py:52-64,

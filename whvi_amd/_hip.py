@@ -127,6 +127,10 @@ def _declare_f3(lib):
         fn = getattr(lib, "whvi_fused_shs_bwd_" + sfx)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+    lib.whvi_fused_shs_stacked_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_supported.argtypes = [i32, i64]
+    lib.whvi_fused_shs_stacked_f32.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_f32.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -435,6 +439,50 @@ def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: tor
                 FUSED_SRC_SHARED if shared else 0, _stream(grad_y))
     _check(rc, "whvi_fused_shs_bwd")
     return grad_x, grad_a, grad_b, grad_c
+
+
+def fused_shs_stacked_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """Shapes the one-launch rectangular fastfood layer covers (``whvi_fused_shs_stacked_supported``, restated: no library
+    needed): float32, 64 <= D <= 2048 and ``n_blocks >= 1`` triples of ``D`` floats within 64 KiB of LDS."""
+    if dtype != torch.float32 or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return 64 <= d <= 2048 and n_blocks >= 1 and 12 * d * n_blocks <= 65536
+
+
+def fused_shs_stacked(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int, sample_stride: int,
+                      shared: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """``out[r, j * D + n] = a[j, n] * fwht(b[j, s(r)] * fwht(c[j] * src[r]))[n]`` for all ``J`` blocks in ONE launch
+    (whvi_fused_shs_stacked_f32): ``(n_samples * sample_stride, J * D)`` from ``src`` ``(n_samples * sample_stride, D)`` in
+    (sample, row) order -- or ``(sample_stride, D)`` with ``shared``, read by every sample -- ``a, c`` ``(J, D)`` and ``b``
+    ``(J, n_samples, D)``.  Block ``j`` of the result has the bits of ``fused_shs(src, a[j], b[j], c[j])``.  ``out``: a
+    contiguous, 16-byte aligned ``(n_samples * sample_stride, J * D)`` float32 tensor to write instead of a new one."""
+    S, stride = int(n_samples), int(sample_stride)
+    if src.device.type != "cuda" or src.dim() != 2:
+        raise RuntimeError("fused_shs_stacked: src must be a 2-D CUDA tensor")
+    _require_f32_on_one_device("fused_shs_stacked", src.device, (src, a, b, c))
+    d = src.size(1)
+    if a.dim() != 2 or a.size(1) != d:
+        raise RuntimeError("fused_shs_stacked: a must be (n_blocks, D)")
+    J = a.size(0)
+    if not fused_shs_stacked_supported(torch.float32, d, J):
+        raise RuntimeError(f"fused_shs_stacked: {J} blocks of {d} elements are outside the supported range "
+                           "(64 <= D <= 2048, 12 * D * n_blocks <= 65536)")
+    rows = S * stride
+    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d):
+        raise RuntimeError("fused_shs_stacked: operand shapes do not match (src rows must be n_samples * sample_stride, or "
+                           "sample_stride when shared; a, c (J, D); b (J, S, D))")
+    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
+    if out is None:
+        out = torch.empty((rows, J * d), dtype=torch.float32, device=src.device)
+    elif not out.is_contiguous() or tuple(out.shape) != (rows, J * d) or out.dtype != torch.float32 or out.device != src.device:
+        raise RuntimeError("fused_shs_stacked: bad out tensor")
+    if rows == 0:
+        return out
+    with _OnDevice(src.device):
+        rc = lib().whvi_fused_shs_stacked_f32(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride,
+                                              d.bit_length() - 1, FUSED_SRC_SHARED if shared else 0, _stream(src))
+    _check(rc, "whvi_fused_shs_stacked")
+    return out
 
 
 def reparam_kl(g_mu: torch.Tensor, g_rho: torch.Tensor, eps: torch.Tensor, lambda_: float):

@@ -22,6 +22,11 @@ ONE launch of ``whvi_fused_shs_ex_f16 / _bf16`` -- float32 parameters, float32 a
 stored, 2 bytes read + 2 written per element -- and returns the input's dtype.  With ``fused_backward = True`` as well, a
 backward that wants a parameter gradient is ONE launch of ``whvi_fused_shs_bwd_f16 / _bf16`` (6 bytes per element, float32
 sums, ``grad_x`` rounded once) instead of two float32 upcasts and the float32 chain; both flags default to False.
+
+Rectangular layers (``WHVIFastfoodStackedMatrix``, ``WHVILinear(..., mode="fastfood_stacked")``): the paper's stacking -- the
+input zero-padded to ``D = 2^ceil(log2 n_in)``, ``J = ceil(n_out / D)`` independent square operators applied to it, their
+outputs concatenated and the surplus columns dropped.  On the GPU the float32 forward is ONE launch of
+``whvi_fused_shs_stacked_f32`` that reads a row once and writes all ``J`` blocks side by side.
 """
 import torch
 import torch.nn as nn
@@ -30,7 +35,7 @@ from torch.autograd.function import once_differentiable
 
 from whvi_amd.utils import is_pow_of_2
 
-__all__ = ["FastfoodFunction", "WHVIFastfoodMatrix"]
+__all__ = ["FastfoodFunction", "WHVIFastfoodMatrix", "FastfoodStackedFunction", "WHVIFastfoodStackedMatrix"]
 
 
 def _fwht(x):
@@ -86,6 +91,72 @@ def _scale_fwht(x, vec, n_samples=1, sample_stride=1):
     return _fwht(vec * x)
 
 
+def _fastfood_backward(grad_y, x, a, b, c, S, stride, shared, keep_half, fused_backward, needs):
+    """``(grad_x, grad_a, grad_b, grad_c)`` of ``y = a * fwht(b_s * fwht(c * x))`` -- the backward of ``FastfoodFunction`` (its
+    docstring describes the routes), also run per block by ``FastfoodStackedFunction``.  ``keep_half`` / ``fused_backward``: the
+    flags as the forward resolved them; ``needs``: which of ``x, a, b, c`` want a gradient (the others come back as None)."""
+    need_x, need_a, need_b, need_c = needs
+    grad_y = grad_y.contiguous()
+    grad_x = grad_a = grad_b = grad_c = None
+    x_dtype = x.dtype
+    if keep_half:
+        if need_x and not (need_a or need_b or need_c or shared):
+            return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None
+        if (fused_backward and (need_a or need_b or need_c) and not (shared and need_x)
+                and grad_y.dtype == x.dtype and grad_y.device == x.device
+                and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
+                and grad_y.size(0) == S * stride):
+            from whvi_amd import _hip
+            if _hip.fused_shs_bwd16_supported(x.dtype, x.size(1)):
+                # ONE 16-bit launch: no float32 copy of x or grad_y, the sums in float32 (a shared x wants no gradient here)
+                grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=shared,
+                                                                    need_x=need_x)
+                return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
+                        grad_c if need_c else None)
+        x, grad_y = x.float(), grad_y.float()
+    if (fused_backward and not keep_half and (need_a or need_b or need_c) and x.dtype == torch.float32 and grad_y.dtype == torch.float32
+            and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
+            and grad_y.size(0) == S * stride):
+        from whvi_amd import _hip
+        if _hip.fused_shs_bwd_supported(torch.float32, x.size(1)):
+            # ONE launch: t1, u, v, w stay in registers, the three sums leave the chip as one partial per block
+            grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=shared,
+                                                                need_x=need_x)
+            if shared and grad_x is not None:
+                grad_x = grad_x.view(S, stride, -1).sum(dim=0)
+            return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
+                    grad_c if need_c else None)
+    if shared:
+        # every sample read the same rows: their gradients add up (what autograd does for an expanded input)
+        fold = lambda g: None if g is None else g.view(S, stride, -1).sum(dim=0)   # noqa: E731
+        x = x.repeat(S, 1)
+    else:
+        fold = lambda g: g                                                        # noqa: E731
+    if need_x and not (need_a or need_b or need_c):
+        return fold(_pipeline(grad_y, c, b, a, S, stride)).to(x_dtype), None, None, None
+    # Every transform of the backward pass is "scale, then FWHT" (optionally scaled again): ONE launch each through the
+    # one-transform form of the fused kernel where it exists, the multiply + plain transform elsewhere -- the same
+    # roundings either way (tests/test_streaming_parity_gpu.py pins the launch to multiply + fwht_rows bit for bit)
+    t1 = _scale_fwht(x, c)                              # forward intermediate fwht(c * x), recomputed
+    if need_a:
+        grad_a = (grad_y * _scale_fwht(t1, b, S, stride)).sum(dim=0)
+    v = _scale_fwht(grad_y, a)                          # gradient at (b * t1)
+    if need_b:
+        prod = v * t1
+        if stride * S == x.size(0):                     # (S, rows_per_sample, D) layout: one segmented sum
+            grad_b = prod.view(S, stride, -1).sum(dim=1)
+        else:
+            rows = torch.arange(x.size(0), device=x.device) // stride % S
+            grad_b = torch.zeros_like(b).index_add_(0, rows, prod)
+    if need_c or need_x:
+        w = _scale_fwht(v, b, S, stride)                # gradient at (c * x)
+        if need_c:
+            grad_c = (w * x).sum(dim=0)
+        if need_x:
+            grad_x = fold(c * w).to(x_dtype)
+    return grad_x, grad_a, grad_b, grad_c
+
+
 class FastfoodFunction(torch.autograd.Function):
     """``y = a * fwht(b_s * fwht(c * x))`` on rows ``(n_samples, rows_per_sample, D)`` flattened, ``b``: (S, D).
 
@@ -127,67 +198,9 @@ class FastfoodFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_y):
         x, a, b, c = ctx.saved_tensors
-        S, stride = ctx.n_samples, ctx.sample_stride
-        grad_y = grad_y.contiguous()
-        need_x, need_a, need_b, need_c = ctx.needs_input_grad[:4]
-        grad_x = grad_a = grad_b = grad_c = None
-        x_dtype = x.dtype
-        if ctx.keep_half:
-            if need_x and not (need_a or need_b or need_c or ctx.shared):
-                return _pipeline(grad_y, c, b, a, S, stride, keep_half=True), None, None, None, None, None, None, None, None
-            if (ctx.fused_backward and (need_a or need_b or need_c) and not (ctx.shared and need_x)
-                    and grad_y.dtype == x.dtype and grad_y.device == x.device
-                    and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
-                    and grad_y.size(0) == S * stride):
-                from whvi_amd import _hip
-                if _hip.fused_shs_bwd16_supported(x.dtype, x.size(1)):
-                    # ONE 16-bit launch: no float32 copy of x or grad_y, the sums in float32 (a shared x wants no gradient here)
-                    grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
-                                                                        need_x=need_x)
-                    return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
-                            grad_c if need_c else None, None, None, None, None, None)
-            x, grad_y = x.float(), grad_y.float()
-        if (ctx.fused_backward and not ctx.keep_half and (need_a or need_b or need_c) and x.dtype == torch.float32 and grad_y.dtype == torch.float32
-                and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))
-                and grad_y.size(0) == S * stride):
-            from whvi_amd import _hip
-            if _hip.fused_shs_bwd_supported(torch.float32, x.size(1)):
-                # ONE launch: t1, u, v, w stay in registers, the three sums leave the chip as one partial per block
-                grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
-                                                                    need_x=need_x)
-                if ctx.shared and grad_x is not None:
-                    grad_x = grad_x.view(S, stride, -1).sum(dim=0)
-                return (grad_x, grad_a if need_a else None, grad_b.view_as(b) if need_b else None,
-                        grad_c if need_c else None, None, None, None, None, None)
-        if ctx.shared:
-            # every sample read the same rows: their gradients add up (what autograd does for an expanded input)
-            fold = lambda g: None if g is None else g.view(S, stride, -1).sum(dim=0)   # noqa: E731
-            x = x.repeat(S, 1)
-        else:
-            fold = lambda g: g                                                        # noqa: E731
-        if need_x and not (need_a or need_b or need_c):
-            return fold(_pipeline(grad_y, c, b, a, S, stride)).to(x_dtype), None, None, None, None, None, None, None, None
-        # Every transform of the backward pass is "scale, then FWHT" (optionally scaled again): ONE launch each through the
-        # one-transform form of the fused kernel where it exists, the multiply + plain transform elsewhere -- the same
-        # roundings either way (tests/test_streaming_parity_gpu.py pins the launch to multiply + fwht_rows bit for bit)
-        t1 = _scale_fwht(x, c)                              # forward intermediate fwht(c * x), recomputed
-        if need_a:
-            grad_a = (grad_y * _scale_fwht(t1, b, S, stride)).sum(dim=0)
-        v = _scale_fwht(grad_y, a)                          # gradient at (b * t1)
-        if need_b:
-            prod = v * t1
-            if stride * S == x.size(0):                     # (S, rows_per_sample, D) layout: one segmented sum
-                grad_b = prod.view(S, stride, -1).sum(dim=1)
-            else:
-                rows = torch.arange(x.size(0), device=x.device) // stride % S
-                grad_b = torch.zeros_like(b).index_add_(0, rows, prod)
-        if need_c or need_x:
-            w = _scale_fwht(v, b, S, stride)                # gradient at (c * x)
-            if need_c:
-                grad_c = (w * x).sum(dim=0)
-            if need_x:
-                grad_x = fold(c * w).to(x_dtype)
-        return grad_x, grad_a, grad_b, grad_c, None, None, None, None, None
+        grads = _fastfood_backward(grad_y, x, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half,
+                                   ctx.fused_backward, ctx.needs_input_grad[:4])
+        return (*grads, None, None, None, None, None)
 
 
 class WHVIFastfoodMatrix(nn.Module):
@@ -256,3 +269,95 @@ class WHVIFastfoodMatrix(nn.Module):
     def forward(self, x):
         out = self.forward_mc(x.reshape(-1, self.D), 1)[0].reshape(x.shape)
         return out
+
+
+class FastfoodStackedFunction(torch.autograd.Function):
+    """``y[:, j * D:(j + 1) * D] = a[j] * fwht(b[j, s] * fwht(c[j] * x))`` for ``j = 0 .. J - 1``: ``J`` square fastfood operators
+    on the same rows ``(n_samples, rows_per_sample, D)`` flattened, side by side.  ``a, c``: (J, D); ``b``: (J, S, D).
+
+    Forward: ONE launch of ``whvi_fused_shs_stacked_f32`` for float32 CUDA tensors that ``_hip.fused_shs_stacked_supported``
+    covers -- the row read once, ``J`` segments written -- and otherwise (host tensors, other dtypes, D < 64 or D > 2048, more
+    blocks than fit the launch's LDS) the concatenation of ``FastfoodFunction``'s forward per block, which block ``j`` of the
+    launch equals bit for bit.  Backward: per block, what ``FastfoodFunction.backward`` runs on that block's columns of
+    ``grad_y`` (``keep_half`` and ``fused_backward`` as there); the blocks' ``grad_x`` add up.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False):
+        ctx.fused_backward = bool(fused_backward) and x.device.type == "cuda"
+        ctx.save_for_backward(x, a, b, c)
+        ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
+        ctx.keep_half = bool(keep_half) and x.device.type == "cuda" and x.dtype in _HALF
+        if x.device.type == "cuda" and all(t.dtype == torch.float32 and t.device == x.device for t in (x, a, b, c)):
+            from whvi_amd import _hip
+            if _hip.fused_shs_stacked_supported(torch.float32, x.size(1), a.size(0)):
+                return _hip.fused_shs_stacked(x, a, b, c, ctx.n_samples, ctx.sample_stride, shared=ctx.shared)
+        return torch.cat([_pipeline(x, a[j], b[j], c[j], ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half)
+                          for j in range(a.size(0))], dim=1)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, a, b, c = ctx.saved_tensors
+        J, D = a.shape
+        need_x, need_a, need_b, need_c = ctx.needs_input_grad[:4]
+        blocks = grad_y.view(grad_y.size(0), J, D)
+        grad_x, per_block = None, []
+        for j in range(J):
+            gx, ga, gb, gc = _fastfood_backward(blocks[:, j].contiguous(), x, a[j], b[j], c[j], ctx.n_samples, ctx.sample_stride,
+                                                ctx.shared, ctx.keep_half, ctx.fused_backward, (need_x, need_a, need_b, need_c))
+            if gx is not None:
+                grad_x = gx if grad_x is None else grad_x + gx
+            per_block.append((ga, gb, gc))
+        grad_a, grad_b, grad_c = (torch.stack([g[i] for g in per_block]) if need else None
+                                  for i, need in enumerate((need_a, need_b, need_c)))
+        return grad_x, grad_a, grad_b, grad_c, None, None, None, None, None
+
+
+class WHVIFastfoodStackedMatrix(nn.Module):
+    """Rectangular (n_out, n_in) WHVI layer in fastfood mode: ``stack`` square ``WHVIFastfoodMatrix`` blocks of width
+    ``D_in = 2^ceil(log2 n_in)`` applied to the zero-padded input, their outputs concatenated and narrowed to ``n_out``
+    (dimensions: ``WHVIStackedMatrix.setup_dimensions``).  Parameters ``weight_matrices.<j>.{s1, s2, g_mu, g_rho}`` (+ optional
+    ``bias`` (1, D_out)) -- the checkpoint keys and the creation order of ``WHVIStackedMatrix``, so its state dict loads and the
+    same seed gives the same parameters."""
+    fused_backward = False    # as on WHVIFastfoodMatrix: True = each block's backward is one launch where FastfoodFunction's is
+    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (per-block launches)
+
+    def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
+        super().__init__()
+        from whvi_amd.weights import WHVIStackedMatrix
+        self.n_in, self.n_out, self.lambda_ = n_in, n_out, lambda_
+        self.D_in, self.D_out, self.padding, self.stack = WHVIStackedMatrix.setup_dimensions(n_in, n_out)
+        self.weight_matrices = nn.ModuleList([WHVIFastfoodMatrix(self.D_in, lambda_=lambda_) for _ in range(self.stack)])
+        self.bias = nn.Parameter(torch.zeros(1, self.D_out)) if bias else None
+
+    @property
+    def kl(self):
+        return sum(m.kl for m in self.weight_matrices)
+
+    def _stacked(self, name):
+        """(stack, D_in) tensor of one per-block vector."""
+        return torch.stack([getattr(m, name) for m in self.weight_matrices])
+
+    def forward_mc(self, x, n_samples):
+        """(batch, n_in) or (n_samples, batch, n_in) -> (n_samples, batch, n_out); sample k of block j uses row ``[j, k]`` of
+        one ``randn(stack, n_samples, D_in)`` draw."""
+        s1, s2, g_mu = self._stacked("s1"), self._stacked("s2"), self._stacked("g_mu")
+        eps = torch.randn(self.stack, n_samples, self.D_in, device=g_mu.device)
+        g = g_mu.unsqueeze(1) + F.softplus(self._stacked("g_rho")).unsqueeze(1) * eps                 # (J, S, D)
+        if self.padding > 0:
+            x = F.pad(x, (0, self.padding))
+        half = False
+        if self.keep_half and x.device.type == "cuda" and x.dtype in _HALF and s1.dtype == torch.float32:
+            from whvi_amd import _hip
+            half = _hip.fused_supported(x.dtype, self.D_in)
+        shared = x.dim() == 2                  # a (batch, D) input shared by all samples: read by every sample, never expanded
+        batch = x.size(0) if shared else x.size(1)
+        rows = x.contiguous() if shared else x.reshape(n_samples * batch, self.D_in).contiguous()
+        out = FastfoodStackedFunction.apply(rows, s1, g, s2, n_samples, batch, shared, half, self.fused_backward)
+        out = out.view(n_samples, batch, self.D_out)        # (the launch always writes pitch D_out)
+        if self.bias is not None:
+            out = out + (self.bias.to(x.dtype) if half else self.bias)
+        return out[..., :self.n_out]
+
+    def forward(self, x):
+        return self.forward_mc(x.reshape(-1, self.n_in), 1)[0].reshape(*x.shape[:-1], self.n_out)

@@ -31,8 +31,11 @@ def _choose_parameterisation(n_in, n_out, lambda_, bias, mode="reference"):
         if n_in != n_out or not is_pow_of_2(n_in):
             raise ValueError("mode='fastfood' is implemented for square power-of-two layers")
         return WHVIFastfoodMatrix(n_in, lambda_=lambda_, bias=bias)
+    if mode == "fastfood_stacked":
+        from whvi_amd.fastfood import WHVIFastfoodStackedMatrix
+        return WHVIFastfoodStackedMatrix(n_in, n_out, lambda_=lambda_, bias=bias)
     if mode != "reference":
-        raise ValueError("mode must be 'reference' or 'fastfood'")
+        raise ValueError("mode must be 'reference', 'fastfood' or 'fastfood_stacked'")
     if n_in == 1:
         return WHVIColumnMatrix(n_out, lambda_=lambda_, bias=bias)
     if n_out == 1:
@@ -51,7 +54,8 @@ class WHVILinear(nn.Module, WHVI):
     ``mode`` (keyword, not in the reference): ``"reference"`` (default) reproduces the reference as written;
     ``"fastfood"`` opts in to the textbook operator S1 H diag(g) H S2 applied to activations without materialising W
     (``whvi_amd.fastfood``) -- same parameters and KL, different (non-diagonal) weight matrix, square power-of-two
-    layers only."""
+    layers only; ``"fastfood_stacked"`` builds the same operator for ANY ``n_in``, ``n_out`` by stacking square blocks on the
+    zero-padded input (``whvi_amd.fastfood.WHVIFastfoodStackedMatrix``: one launch for all blocks on the GPU)."""
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False, mode="reference"):
         super().__init__()
