@@ -55,6 +55,30 @@ def test_shipped_library_reads_no_environment():
             assert "getenv" not in text, name
 
 
+def test_every_tuning_switch_is_driven():
+    """A measurement switch is a second code path inside the shipped kernels, so it exists only while something sets it:
+    every WHVI_* switch tuning.hpp gives a default or lists in its #error guard, and every environment name the sources
+    pass to WHVI_TUNE_ENV, appears by its full name in a script under tools/ or in a test.  A switch whose question is
+    settled is retired with its production value folded in (the numbers stay beside the code that ships)."""
+    csrc = os.path.join(ROOT, "whvi_amd", "csrc")
+    tuning = open(os.path.join(csrc, "tuning.hpp")).read()
+    switches = set(re.findall(r"#\s*define\s+(WHVI_[A-Z0-9_]+)[ \t]+\S", tuning))       # object-like macros with a value
+    guard = tuning[tuning.index("#else"):tuning.index("#error")]
+    switches |= set(re.findall(r"defined\((WHVI_[A-Z0-9_]+)\)", guard))
+    for name in os.listdir(csrc):
+        if name.endswith((".hpp", ".hip")):
+            switches |= set(re.findall(r'WHVI_TUNE_ENV\("(WHVI_[A-Z0-9_]+)"\)', open(os.path.join(csrc, name)).read()))
+    assert len(switches) >= 8, switches            # the patterns above still find them
+    drivers = ""
+    for folder in ("tools", "tests"):
+        for name in sorted(os.listdir(os.path.join(ROOT, folder))):
+            path = os.path.join(ROOT, folder, name)
+            if os.path.isfile(path) and os.path.abspath(path) != os.path.abspath(__file__):
+                drivers += open(path, errors="replace").read()
+    undriven = sorted(s for s in switches if not re.search(s + r"(?![A-Za-z0-9_])", drivers))     # (-DNAME: no \b in front)
+    assert undriven == [], f"no script under tools/ and no test sets {undriven}: retire them (fold the production value in)"
+
+
 def test_argument_checks_without_gpu():
     from whvi_amd import _hip
     L = _hip.lib()

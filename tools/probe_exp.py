@@ -1,5 +1,5 @@
-"""tools/probe_exp.py -- interleaved A/B of experimental builds of the f32 FWHT kernel (whvi_amd/_exp/*.so,
-built by hand with -DWHVI_EXP_*) against the production library, same process, same buffer."""
+"""tools/probe_exp.py -- interleaved A/B of experimental builds of the f32 FWHT kernel (whvi_amd/_exp/libexp_*.so and
+libwhvi_hip_ab_*.so, built by hand from edited sources or with a -D switch of tuning.hpp) against the production library, same process, same buffer."""
 import ctypes, glob, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

@@ -1,5 +1,5 @@
-"""Interleaved A/B of experimental builds of the fused kernel (whvi_amd/_exp/libexpf_*.so, built by hand with
--DWHVI_FUSED_*) against the production library: config 3 (D = 2048) and D = 4096, 4 GiB in place."""
+"""Interleaved A/B of experimental builds of the fused kernel (whvi_amd/_exp/libexpf_*.so, built by hand from edited
+sources) against the production library: config 3 (D = 2048) and D = 4096, 4 GiB in place."""
 import ctypes, glob, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

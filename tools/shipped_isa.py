@@ -6,7 +6,13 @@ llvm-readelf --notes, llvm-objdump -d).  tests/test_build.py uses it to pin the 
 the streaming kernels were tuned for (9 % of the headline rate hangs on how 16 stores are issued).
 
     python tools/shipped_isa.py 'fwht_rows_kernel<float, 12, 16, 0, false, true, 256, 1, false>'
-    python tools/shipped_isa.py --lib whvi_amd/_exp/libwhvi_hip_x.so 'wbar_fwd_kernel<float, 11'"""
+    python tools/shipped_isa.py --lib whvi_amd/_exp/libwhvi_hip_x.so 'wbar_fwd_kernel<float, 11'
+    python tools/shipped_isa.py --against ../parent/whvi_amd/libwhvi_hip.so     # did a source change move any shipped code?
+
+--against OTHER_LIB compares the library with another build of it, kernel by kernel: the kernels only one of them has, those
+whose metadata differs, those whose instruction text differs and the code objects whose .rodata (the kernel descriptors)
+differs; the exit status is non-zero if there is any.  It compares text and metadata, not bytes: two builds of the same
+sources differ in bytes."""
 import os
 import re
 import shutil
@@ -155,6 +161,40 @@ def store_data_hazards(code_object, wait_states=2):
     return found
 
 
+def compare(lib, other):
+    """Differences between two built libraries as dict(kernels, only_in_one, metadata, instructions, rodata): the number of
+    kernels both have, and the names (demangled; rodata: one kernel of the code object) of what differs."""
+    fields = ("vgprs", "agprs", "sgprs", "scratch", "lds")
+
+    def contents(shipped):
+        name_of = {k["mangled"]: name for name, k in shipped.kernels.items()}
+        text, rodata = {}, {}
+        for obj in sorted({k["code_object"] for k in shipped.kernels.values()}):
+            dis = subprocess.run([f"{LLVM}/llvm-objdump", "-d", "--no-show-raw-insn", obj], check=True, capture_output=True,
+                                 text=True).stdout
+            symbol = None
+            for line in dis.splitlines():
+                s = _SYMBOL.match(line)
+                m = None if s else re.match(r"^\s+([a-z_0-9]+)\s*(.*?)\s*(//.*)?$", line)
+                if s:
+                    symbol = name_of.get(s.group(1))
+                    text.setdefault(symbol, [])
+                elif m and symbol is not None:
+                    text[symbol].append((m.group(1), m.group(2)))
+            first = min(n for n, k in shipped.kernels.items() if k["code_object"] == obj)
+            rodata[first] = subprocess.run([f"{LLVM}/llvm-objdump", "-s", "-j", ".rodata", obj], check=True, capture_output=True,
+                                           text=True).stdout.split("Contents of section", 1)[-1]
+        return text, rodata
+
+    with ShippedLibrary(lib) as a, ShippedLibrary(other) as b:
+        (text_a, ro_a), (text_b, ro_b) = contents(a), contents(b)
+        both = sorted(set(a.kernels) & set(b.kernels))
+        return dict(kernels=len(both), only_in_one=sorted(set(a.kernels) ^ set(b.kernels)),
+                    metadata=[n for n in both if any(a.kernels[n][f] != b.kernels[n][f] for f in fields)],
+                    instructions=[n for n in both if text_a.get(n) != text_b.get(n) or not text_a.get(n)],
+                    rodata=sorted(n for n in set(ro_a) | set(ro_b) if ro_a.get(n) != ro_b.get(n)))
+
+
 def main():
     args = [a for a in sys.argv[1:]]
     lib = DEFAULT_LIB
@@ -162,6 +202,12 @@ def main():
         i = args.index("--lib")
         lib = args[i + 1]
         del args[i:i + 2]
+    if "--against" in args:
+        diff = compare(lib, args[args.index("--against") + 1])
+        print(f"{diff['kernels']} kernels in both {lib} and {args[args.index('--against') + 1]}")
+        for what in ("only_in_one", "metadata", "instructions", "rodata"):
+            print(f"{what}: {len(diff[what])} differ" + "".join(f"\n    {n}" for n in diff[what]))
+        sys.exit(1 if any(diff[w] for w in ("only_in_one", "metadata", "instructions", "rodata")) else 0)
     pattern = re.compile(args[0]) if args else None
     with ShippedLibrary(lib) as shipped:
         print(f"{len(shipped.kernels)} kernels in {lib}; with scratch: {sum(1 for k in shipped.kernels.values() if k['scratch'])}")

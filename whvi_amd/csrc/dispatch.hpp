@@ -186,8 +186,8 @@ inline void launch_rows(void *dst, const void *src, int64_t n_chunks, int varian
                 // (6.40) -- so the drop-in entry point takes that and keeps the sign of zero; the signed network is opt-in
                 // (signed_lanes), 1024-thread blocks without the barrier (6.03-6.07) only for rows shorter than 64.
                 // profiles/r04/stream_forms_store_spacing_ab.log
-                constexpr bool F64_SIGNED = sizeof(T) == 8 && LOG2D >= 6 && WHVI_F64_STREAM_FORM == 2;
-                if (exp_big_blocks || (sizeof(T) == 8 && (LOG2D < 6 || WHVI_F64_STREAM_FORM == 0))) WHVI_LAUNCH(POLICY_DPP, false, true, BIG);
+                constexpr bool F64_SIGNED = sizeof(T) == 8 && LOG2D >= 6;
+                if (exp_big_blocks || (sizeof(T) == 8 && LOG2D < 6)) WHVI_LAUNCH(POLICY_DPP, false, true, BIG);
                 else if (!signed_lanes && sizeof(T) == 8) {
                     note_launch<T>("fwht_rows_kernel", LOG2D, K, POLICY_DPP, false, true, 256, 1, false);
                     hipLaunchKernelGGL((fwht_rows_kernel<T, LOG2D, K, POLICY_DPP, false, true, 256, 1, false>),
@@ -227,14 +227,14 @@ inline void launch_rows(void *dst, const void *src, int64_t n_chunks, int varian
             else WHVI_LAUNCH(POLICY_DPP, false, false, 256);
         } else {
             // tiles of more than 64 data VGPRs (one row per wave: f32 D = 8192, f64 D = 4096): 256-thread blocks
-            // either way; streams get the non-temporal accesses and the store barrier as well
+            // either way; streams get the non-temporal accesses and the store barrier as well, and the UNSIGNED network
+            // (tried: the signed one here loses, 6.23 vs 6.31)
             if (big && nt) {
-                constexpr bool SG = (sizeof(T) == 8 || std::is_same<T, float>::value) && WHVI_F64_STREAM_FORM == 3;   // tuning: the signed network here loses (6.23 vs 6.31)
-                if constexpr (!SG && std::is_same<T, float>::value && LOG2D == max_single_pass_log2d<T>() && WHVI_WIDE_TILE_WAVES > 0)
+                if constexpr (std::is_same<T, float>::value && LOG2D == max_single_pass_log2d<T>())
                     launch_wide_stream<T>(d, s, n_chunks, n_tiles, st);
                 else {
-                    note_launch<T>("fwht_rows_kernel", LOG2D, K, POLICY_DPP, false, true, 256, 1, SG);
-                    hipLaunchKernelGGL((fwht_rows_kernel<T, LOG2D, K, POLICY_DPP, false, true, 256, 1, SG>),
+                    note_launch<T>("fwht_rows_kernel", LOG2D, K, POLICY_DPP, false, true, 256, 1, false);
+                    hipLaunchKernelGGL((fwht_rows_kernel<T, LOG2D, K, POLICY_DPP, false, true, 256, 1, false>),
                                        dim3((unsigned)((n_tiles + 3) / 4)), dim3(256), 0, st, d, s, n_chunks, n_tiles);
                 }
             } else WHVI_LAUNCH(POLICY_DPP, false, false, 256);

@@ -26,9 +26,9 @@ __device__ __forceinline__ u32x4 uniform_ld16_pitch32(const void *base, uint32_t
     return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 32, byte_offset, 0));
 }
 
-// POLICY: POLICY_DPP = the signed DPP / permlane network of the f32 fused kernel for both transforms (shipped);
-// POLICY_LDS = fwht_tile_lds for both (measurement builds: one private 16.6 KB slab per wave caps a CU at 8 waves, and at
-// 4 once vectors are staged beside the slabs at D >= 2048 -- DESIGN.md 5.2b).
+// POLICY: POLICY_DPP = the signed DPP / permlane network of the f32 fused kernel for both transforms, the one value that is
+// instantiated.  (Tried: fwht_tile_lds for both -- one private 16.6 KB slab per wave caps a CU at 8 waves, and at 4 once
+// vectors are staged beside the slabs at D >= 2048 -- DESIGN.md 5.2b.)
 template <typename T, int LOG2D, int K, bool NT, int POLICY, int STAGE, int BLOCK = 256>
 __global__ void __launch_bounds__(BLOCK)
 fused_shs16_kernel(u32x4 *dst, const u32x4 *src, const float *a, const float *b, const float *c,
@@ -45,7 +45,7 @@ fused_shs16_kernel(u32x4 *dst, const u32x4 *src, const float *a, const float *b,
     static_assert(sizeof(T) == 2 && VEC == 8 && sizeof(A) == 4, "16-bit storage, f32 arithmetic");
     static_assert(LOG2D >= LV && LOG2D <= LV + 6 + ilog2(K), "rows of one chunk up to one tile");
     static_assert(STAGE == STAGE_NONE || SH >= 6, "staging: rows of at least 64 chunks");
-    static_assert(POLICY == POLICY_DPP || K * VEC == 64, "LDS-staged network: 64-register tiles");
+    static_assert(POLICY == POLICY_DPP, "the DPP / permlane network is the only form of this kernel");
     const bool a_per_sample = flags & WHVI_FUSED_A_PER_SAMPLE;
     const bool c_per_sample = flags & WHVI_FUSED_C_PER_SAMPLE;
 
@@ -66,7 +66,6 @@ fused_shs16_kernel(u32x4 *dst, const u32x4 *src, const float *a, const float *b,
     // are written to LDS and the block barrier passes while the tile's loads are still in flight
     extern __shared__ __attribute__((aligned(16))) char whvi_smem[];
     constexpr int NSTAGED = STAGE == STAGE_ABC ? 3 : (STAGE == STAGE_AC ? 2 : 0);
-    constexpr int STAGED = NSTAGED * D;                               // floats of LDS in front of the slabs
     A *const lds_a = reinterpret_cast<A *>(whvi_smem);
     A *const lds_c = lds_a + D;
     A *const lds_b = lds_c + D;
@@ -123,14 +122,10 @@ fused_shs16_kernel(u32x4 *dst, const u32x4 *src, const float *a, const float *b,
         return;
     }
 
-    constexpr bool SIGNED = POLICY == POLICY_DPP;
-    constexpr int SIGN_MID = SIGNED ? fwht_sign_out<VEC, LOG2D>(0) : 0;
-    static_assert(!SIGNED || fwht_sign_out<VEC, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
+    constexpr int SIGN_MID = fwht_sign_out<VEC, LOG2D>(0);
+    static_assert(fwht_sign_out<VEC, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
     auto transform = [&](A (&r)[K][VEC], auto second) {
-        if constexpr (POLICY == POLICY_LDS)
-            fwht_tile_lds<A, VEC, K, LOG2D>(r, lane, reinterpret_cast<A *>(whvi_smem) + STAGED + wave * lds_slab_floats<VEC, K>());
-        else
-            fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, SIGNED, decltype(second)::value ? SIGN_MID : 0>(r, lane);
+        fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, decltype(second)::value ? SIGN_MID : 0>(r, lane);
     };
 
     // rows never straddle tiles; rows of >= 64 chunks (UNIFORM): the row of k-step k -- hence its sample and its vector's

@@ -76,10 +76,9 @@ constexpr int64_t fused_bwd_part_floats(int log2d) { return (int64_t)3 << log2d;
 template <int LOG2D, int K, bool FIRST, int VEC>
 __device__ __forceinline__ void fused_bwd_fwht(float (&r)[K][VEC], int lane)
 {
-    constexpr bool SIGNED = WHVI_FUSED_SIGNED != 0;
-    constexpr int SIGN_MID = SIGNED ? fwht_sign_out<VEC, LOG2D>(0) : 0;
-    static_assert(!SIGNED || fwht_sign_out<VEC, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
-    fwht_tile<float, VEC, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, SIGNED, FIRST ? 0 : SIGN_MID>(r, lane);
+    constexpr int SIGN_MID = fwht_sign_out<VEC, LOG2D>(0);
+    static_assert(fwht_sign_out<VEC, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
+    fwht_tile<float, VEC, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, FIRST ? 0 : SIGN_MID>(r, lane);
 }
 
 // acc = fma(p, q, acc), with the sum pinned to the accumulation half of the wave's register file -- read out, updated, written

@@ -76,11 +76,7 @@ template <typename A> struct Bits;
 template <> struct Bits<float> {
     template <int LB> static __device__ __forceinline__ float partner_dpp(float v)
     {
-        float p = __builtin_bit_cast(float, dpp_xor_u32<LB>(__builtin_bit_cast(uint32_t, v)));
-#ifdef WHVI_EXP_UNFUSED_DPP          // tuning builds: keep v_mov_b32_dpp apart from the add that consumes it (the i32 code shape)
-        asm volatile("" : "+v"(p));
-#endif
-        return p;
+        return __builtin_bit_cast(float, dpp_xor_u32<LB>(__builtin_bit_cast(uint32_t, v)));
     }
     // upper lane of the pair computes partner - v, lower lane v + partner; folding the sign
     // into v first keeps it at one v_xor + one (DPP-fused) v_add.  p + (-v) == p - v exactly.
@@ -247,7 +243,8 @@ __device__ __forceinline__ void add2(A &a0, A &a1, A x0, A x1)
 // the issue slots of those stages but want even-aligned register pairs: in the plain streaming kernel that costs
 // 38 VGPRs (145 vs 107 = 3 vs 4 waves per SIMD) and 1.5 % of the stream at D = 4096, so it passes PK = false; the
 // fused / weight kernels (more VALU work per byte) are faster with it.
-//
+constexpr int FUSED_PKMASK = 2;   // the fused pipeline's kernels: packed adds in the permlane stages only (TUs built with -fno-slp-vectorize)
+
 // SIGNED (f32 / f64, POLICY_DPP only): the DPP lane stages as ONE fused multiply-add per element instead of a sign fold
 // plus an add.  Every lane computes  own + s * partner  with s = +/-1 (exact: the same bits as own +/- partner), which is
 // the butterfly's result in the lower lane of a pair and its NEGATIVE in the upper lane; instead of repairing that, the

@@ -232,16 +232,14 @@ template <bool NT = false>
 __device__ __forceinline__ u32x4 uniform_ld16(const void *base, uint32_t bytes, int lane, int byte_offset)
 {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, byte_offset, NT ? (1 << 1) : WHVI_VEC_AUX));
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16, byte_offset, NT ? (1 << 1) : 0));
 }
 // the same load with the low 4 KiB of the byte offset in the instruction's immediate field and only the rest as the scalar
 // offset: consecutive chunks then share a scalar offset four at a time and issue back to back (no s_movk between them)
-template <bool NT = false>
 __device__ __forceinline__ u32x4 uniform_ld16_grouped(const void *base, uint32_t bytes, int lane, int byte_offset)
 {
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(base), 0, (int)bytes, 0x00020000);
-    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16 + (byte_offset & 4095), byte_offset & ~4095,
-                                                                            NT ? (1 << 1) : WHVI_VEC_AUX));
+    return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane * 16 + (byte_offset & 4095), byte_offset & ~4095, 0));
 }
 // the store counterpart; writes beyond `bytes` are dropped.  NT: write-through + non-temporal (see tile_store_stream)
 template <bool NT, bool WRITE_THROUGH = true>
@@ -262,7 +260,7 @@ template <typename T, int K, int ALIGN> constexpr int rows_waves_per_eu()
 {
     // (f32 only: f64 gains nothing from the third wave, 5.88 vs 5.91 TB/s)
     constexpr bool wide = K * Elem<T>::VEC * (int)sizeof(typename Elem<T>::acc) / 4 > 64 && std::is_same<T, float>::value;
-    return (wide && ALIGN >= 1 && WHVI_WIDE_TILE_WAVES > 0) ? WHVI_WIDE_TILE_WAVES : WHVI_ROWS_WAVES_PER_EU;
+    return (wide && ALIGN >= 1) ? 3 : 1;
 }
 
 // ---- batched row FWHT ------------------------------------------------------------------------
@@ -330,7 +328,7 @@ fwht_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_chunks, int64_t n_tiles
         // network); profiles/r02/plateau_*.
         if constexpr (SIGNED) {
             static_assert(POLICY == POLICY_DPP && !std::is_same<A, int32_t>::value, "signed form: floating-point arithmetic, DPP network");
-            fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, WHVI_ROWS_PKMASK, true, 0>(r, lane);
+            fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, 0, true, 0>(r, lane);
             constexpr int OUT = fwht_sign_out<VEC, LOG2D>(0);
             const A sg = (__builtin_popcount(lane & OUT) & 1) ? (A)-1 : (A)1;
 #pragma unroll
@@ -338,45 +336,19 @@ fwht_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_chunks, int64_t n_tiles
 #pragma unroll
                 for (int c = 0; c < VEC; ++c) r[k][c] = fma_pm(r[k][c], sg, (A)0);
         } else
-            fwht_tile<A, VEC, K, LOG2D, POLICY, WHVI_ROWS_PKMASK>(r, lane);      // no explicit packed adds here: see fwht_tile
+            fwht_tile<A, VEC, K, LOG2D, POLICY, 0>(r, lane);      // no explicit packed adds here: see fwht_tile
     };
 
-#if defined(WHVI_TUNING_BUILD) && defined(WHVI_ROWS_BUFFER_IO)
-    // A/B: bounds-checked buffer accesses from the tile's wave-uniform base (the fused kernel's form) -- no full / partial
-    // branch, no per-chunk addresses
-    auto tile_bytes_of = [&](int64_t tile) -> uint32_t {
-        const int64_t base = tile * TILE;
-        return (uint32_t)((n_chunks - base < TILE ? n_chunks - base : (int64_t)TILE) * 16);
-    };
-    auto load_tile = [&](int64_t tile, u32x4 (&raw)[K]) {
-        const uint32_t bytes = tile_bytes_of(tile);
-#pragma unroll
-        for (int k = 0; k < K; ++k) raw[k] = uniform_ld16<NT>(src + tile * TILE, bytes, lane, k * 1024);
-    };
-    auto store_tile = [&](int64_t tile, A (&r)[K][VEC]) {
-        const uint32_t bytes = tile_bytes_of(tile);
-#pragma unroll
-        for (int k = 0; k < K; ++k) uniform_st16<NT>(dst + tile * TILE, bytes, lane, k * 1024, E::pack(r[k]));
-    };
-#else
     // One-row tiles of 128 data registers: the partial last tile goes through bounds-checked buffer accesses from the
     // tile's wave-uniform base (reads beyond the buffer return zeros, writes are dropped) instead of 32 guarded accesses
     // with a 64-bit compare and an address pair each -- registers the 168-VGPR budget of three waves per SIMD does not have.
-    constexpr bool WIDE = K * VEC * (int)sizeof(A) / 4 > 64 && WHVI_WIDE_TILE_WAVES > 0 && std::is_same<T, float>::value;   // the 3-wave f32 tile, see rows_waves_per_eu
+    constexpr bool WIDE = K * VEC * (int)sizeof(A) / 4 > 64 && std::is_same<T, float>::value;   // the 3-wave f32 tile, see rows_waves_per_eu
     auto load_tile = [&](int64_t tile, u32x4 (&raw)[K]) {
         const int64_t base = tile * TILE;
         const u32x4 *p = src + base + lane;
-        if constexpr (WIDE && NT && WHVI_WIDE_TILE_LOADS == 1) {
-            const int64_t left = n_chunks - base;
-            const uint32_t bytes = (uint32_t)((left < TILE ? left : (int64_t)TILE) * 16);
+        if (base + TILE <= n_chunks) {
 #pragma unroll
-            for (int k = 0; k < K; ++k) raw[k] = uniform_ld16<NT>(src + base, bytes, lane, k * 1024);
-        } else if (base + TILE <= n_chunks) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                raw[k] = ld16<NT>(p + k * 64);
-                if constexpr (WHVI_ROWS_LOAD_SPACING > 0) asm volatile("s_nop %0" ::"n"(WHVI_ROWS_LOAD_SPACING - 1));   // A/B: issue spacing
-            }
+            for (int k = 0; k < K; ++k) raw[k] = ld16<NT>(p + k * 64);
         } else if constexpr (WIDE) {
             const uint32_t bytes = (uint32_t)((n_chunks - base) * 16);
 #pragma unroll
@@ -404,18 +376,6 @@ fwht_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_chunks, int64_t n_tiles
             if constexpr (NT && WHVI_ROWS_STORE_FORM == 1) {        // A/B: chunk offset as the instruction's scalar offset
 #pragma unroll
                 for (int k = 0; k < K; ++k) uniform_st16<true>(dst + base, TILE * 16, lane, k * 1024, E::pack(r[k]));
-            } else if constexpr (NT && WHVI_ROWS_STORE_FORM >= 3) {  // A/B: issue spacing between the stores
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    if constexpr (WHVI_ROWS_STORE_FORM == 5) uniform_st16<true>(dst + base, TILE * 16, lane, k * 1024, E::pack(r[k]));
-                    else tile_store_stream(dst + base, lane, k, E::pack(r[k]), TILE * 16);
-                    if constexpr (WHVI_ROWS_STORE_FORM == 4) __builtin_amdgcn_s_sleep(1);
-                    else if constexpr (WHVI_ROWS_STORE_FORM == 6) asm volatile("s_nop 0");
-                    else asm volatile("s_nop 7");
-                }
-            } else if constexpr (NT && WHVI_ROWS_STORE_FORM == 2) {  // A/B: descending chunk order
-#pragma unroll
-                for (int k = K - 1; k >= 0; --k) tile_store_stream(dst + base, lane, k, E::pack(r[k]), TILE * 16);
             } else if constexpr (NT) {
 #pragma unroll
                 for (int k = 0; k < K; ++k) {
@@ -437,7 +397,6 @@ fwht_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_chunks, int64_t n_tiles
         }
     };
 
-#endif
     if constexpr (!PREFETCH) {
         // plain grid-stride form: with grid == tiles/waves this is one tile per wave and out; only
         // one tile's worth of registers is ever live (fits a 1024-thread block at 128 VGPRs)
@@ -445,16 +404,13 @@ fwht_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_chunks, int64_t n_tiles
             A r[K][VEC];
             {
                 u32x4 raw[K];
-                if constexpr (WHVI_ROWS_SETPRIO == 1) __builtin_amdgcn_s_setprio(3);      // A/B: loads issued at high priority
                 load_tile(t, raw);
-                if constexpr (WHVI_ROWS_SETPRIO == 1) __builtin_amdgcn_s_setprio(0);
 #pragma unroll
                 for (int k = 0; k < K; ++k) E::unpack(raw[k], r[k]);
             }
             if constexpr (ALIGN >= 2) __syncthreads();
             transform(r);
             if constexpr (ALIGN >= 1) __syncthreads();
-            if constexpr (WHVI_ROWS_SETPRIO == 2) __builtin_amdgcn_s_setprio(3);          // A/B: stores issued at high priority
             // (Tried: a block barrier here so the 16 waves store their 256 KiB together.  A copy microbenchmark
             // gains 5 % from it, the real kernel LOSES 8 %: the waves leave the butterflies microseconds apart
             // and the barrier turns that skew into idle time.  profiles/r01/membench_6_store_alignment.log.)
@@ -665,7 +621,7 @@ fwht_block_rows_kernel(u32x4 *dst, const u32x4 *src, int64_t n_rows, uint64_t *t
             constexpr int k = decltype(HALF)::value * (K / 2) + decltype(KK)::value;
             if constexpr (NT) tile_store_stream(tile, lane, k, E::pack(r[k]), TILE * 16);
             else tile[k * 64 + lane] = E::pack(r[k]);
-            if constexpr (NT && WHVI_STORE_SPACING) asm volatile("s_nop 0");     // stores never back to back (5.1, round 3)
+            if constexpr (NT) asm volatile("s_nop 0");     // stores never back to back (5.1, round 3): f32 D = 65536 6.05 -> 6.21-6.26 TB/s
         });
     };
     stamp(0);
@@ -763,7 +719,7 @@ inline FastDiv make_fastdiv(uint32_t d)
 // one scalar per row.  EYE: src is not read; row i of each group is c[i] * e_i (the first group_rows
 // rows of torch.diag(s2), src/weights.py:73).  Every multiply is its own rounding (built with -ffp-contract=off), like
 // the reference's separate matmul_diag_left kernels (src/utils.py:4-12).
-// (WHVI_FUSED_PKMASK = 2, tuning.hpp: packed adds in the permlane stages only; the TU is built with -fno-slp-vectorize)
+// (FUSED_PKMASK = 2, fwht_tile.hpp: packed adds in the permlane stages only; the TU is built with -fno-slp-vectorize)
 //
 // STAGE (AXIS_COL): which scale vectors the BLOCK copies into LDS once, to be multiplied straight out of LDS by its waves:
 //   STAGE_NONE  every vector is fetched from L2 by the wave that needs it (small launches; per-sample a / c when the rows
@@ -875,20 +831,13 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
     const uint32_t tile_bytes = active ? (uint32_t)((n_chunks - base < TILE ? n_chunks - base : (int64_t)TILE) * 16) : 0u;
     u32x4 raw[EYE ? 1 : K];
     if constexpr (!EYE) {
-#if defined(WHVI_TUNING_BUILD) && WHVI_FUSED_TILE_LOADS == 2   /* timing experiment only: every tile taken to be full (WRONG on ragged tails) */
-        if (active) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) raw[k] = ld16<NT>(src + base + k * 64 + lane);
-        }
-        if (false)
-#else
         // Full tiles of 4-byte elements (and short f64 rows): plain global loads behind a wave-uniform branch -- on a bare
         // stream buffer loads are 10 % slower than global loads (5.84 vs 6.48 TB/s on the plain transform) and here
         // 1-3.5 % (f32 D = 512 / 2048 / 4096: shared a / c 6.44 / 6.39 / 6.32 vs 6.37 / 6.38 / 6.31 TB/s, three L2 vectors
         // 5.98 / 5.92 / 5.54 vs 5.84 / 5.72 / 5.42); f64 rows of 2048 and 4096 lose with them (6.18 vs 6.25, and 3.8 vs
         // 5.95: the branch costs the 128-register tile its second wave per SIMD) and keep the bounds-checked buffer loads,
         // as do the partial last tile and idle waves everywhere.  gpurun_out r03_ab_{prod,tl1,tl2}.log
-        constexpr bool GLOBAL_TILE_LOADS = WHVI_FUSED_TILE_LOADS >= 0 ? WHVI_FUSED_TILE_LOADS == 1 : (sizeof(A) == 4 || LOG2D <= 10);
+        constexpr bool GLOBAL_TILE_LOADS = sizeof(A) == 4 || LOG2D <= 10;
         if constexpr (SHARED_SRC) {
             static_assert(AXIS == WHVI_AXIS_COL && SH >= 6, "shared source: column axis, rows of >= 64 chunks");
             constexpr int KPR = (int)CPR / 64;                       // k-steps per row
@@ -903,16 +852,9 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
         if (GLOBAL_TILE_LOADS && tile_bytes == TILE * 16) {
 #pragma unroll
             for (int k = 0; k < K; ++k) raw[k] = ld16<NT>(src + base + k * 64 + lane);
-        } else
-#endif
-        {
+        } else {
 #pragma unroll
-            for (int k = 0; k < K; ++k) {
-                if constexpr (WHVI_FUSED_TILE_LOADS_GROUPED == 1 || (WHVI_FUSED_TILE_LOADS_GROUPED < 0 && sizeof(T) == 8))
-                    raw[k] = uniform_ld16_grouped<NT>(src + base, tile_bytes, lane, k * 1024);      // four per scalar offset: back to back
-                else
-                    raw[k] = uniform_ld16<NT>(src + base, tile_bytes, lane, k * 1024);
-            }
+            for (int k = 0; k < K; ++k) raw[k] = uniform_ld16<NT>(src + base, tile_bytes, lane, k * 1024);
         }
     }
     if constexpr (STAGE != STAGE_NONE) {
@@ -935,7 +877,7 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
 
     // The two transforms of the pipeline use the signed DPP form (fwht_tile.hpp): the first leaves the tile with
     // sigma = (-1)^popcount(lane & mask), the scalings between them commute with it, the second takes it back to 0.
-    constexpr bool SIGNED = WHVI_FUSED_SIGNED && POLICY == POLICY_DPP && !ONE;   // (one transform alone: the unsigned network)
+    constexpr bool SIGNED = POLICY == POLICY_DPP && !ONE;   // (one transform alone: the unsigned network)
     constexpr int SIGN_MID = SIGNED ? fwht_sign_out<VEC, LOG2D>(0) : 0;
     static_assert(!SIGNED || fwht_sign_out<VEC, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
     auto transform = [&](A (&r)[K][VEC], auto second) {
@@ -943,7 +885,7 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
             fwht_tile_lds<A, VEC, K, LOG2D>(r, lane, reinterpret_cast<A *>(whvi_smem) + STAGED +
                                                          wave * lds_slab_floats<VEC, K>());
         else
-            fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, SIGNED, decltype(second)::value ? SIGN_MID : 0>(r, lane);
+            fwht_tile<A, VEC, K, LOG2D, POLICY_DPP, FUSED_PKMASK, SIGNED, decltype(second)::value ? SIGN_MID : 0>(r, lane);
     };
 
     // rows never straddle tiles and TILE is a multiple of CPR or vice versa
@@ -973,7 +915,7 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
             // f64: four loads per scalar offset (the low 3 KiB of the chunk offset as immediates), so the loads of a vector
             // issue back to back instead of one s_movk apart: f64 D = 4096 shared 5.88 -> 6.02 TB/s, per-sample D <= 2048
             // +1 %; f32 +-0.2 % either way (profiles/r03/fused_vector_load_issue_ab.log) and keeps the plain form
-            if constexpr (WHVI_VEC_LOAD_GROUPED == 1 || (WHVI_VEC_LOAD_GROUPED < 0 && sizeof(T) == 8))
+            if constexpr (sizeof(T) == 8)
                 E::unpack(uniform_ld16_grouped(rb.p[k / CHUNKS_PER_ROW_HERE], (uint32_t)sizeof(T) << LOG2D, lane,
                                                (k % CHUNKS_PER_ROW_HERE) * 1024), out);
             else
@@ -1026,8 +968,7 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
     // and all of the vector up front): f32 with three L2 vectors D = 512 5.67 / 5.72 / 5.87, D = 2048 5.61 / 5.64 / 5.75,
     // D = 4096 5.42 / 5.44 / 5.22; f64 D = 512 5.53 / 5.59 / 5.42, D = 2048 5.38 / 5.41 / 5.19; one f64 row of 4096 per
     // wave with a / c staged (only b comes from L2) 5.72 / 5.79 / 5.91.
-    constexpr int EIGHTHS = WHVI_FUSED_UPFRONT_8THS > 0 ? WHVI_FUSED_UPFRONT_8THS
-                          : (BIG_TILE && STAGE != STAGE_NONE) ? 8
+    constexpr int EIGHTHS = (BIG_TILE && STAGE != STAGE_NONE) ? 8
                           : (sizeof(A) == 4 && STAGE == STAGE_NONE && LOG2D <= 11) ? 8
                           : (STAGE == STAGE_NONE ? 6 : 5);
     constexpr int UPFRONT = K >= 4 ? (K * EIGHTHS) / 8 : K;
@@ -1094,24 +1035,13 @@ fused_shs_kernel(u32x4 *dst, const u32x4 *src, const T *a, const T *b, const T *
         else scale_chunkwise(a, a_per_sample);
     }
     if constexpr (NT) __syncthreads();          // the block's 4 waves write their 64 KiB back together
-    if constexpr (SHARED_SRC && NT && WHVI_FUSED_SHARED_GLOBAL_STORES) {
-        // A/B (measurement builds): the write-dominated launch on a shared, cache-resident source with back-to-back global
-        // stores like the write-only weight construction -- it LOSES (one transform per sample: 5.66 -> 5.25 TB/s written at
-        // D = 2048, 5.64 -> 5.32 at D = 512; two transforms: +-1 %), the spaced buffer stores below stay
-        if (tile_bytes == (uint32_t)(64 * K * 16)) {
-            u32x4 *q = dst + base + lane;
+    // Tried on a shared, cache-resident source (the write-dominated launch): back-to-back global stores like the write-only
+    // weight construction -- it LOSES (one transform per sample: 5.66 -> 5.25 TB/s written at D = 2048, 5.64 -> 5.32 at
+    // D = 512; two transforms: +-1 %), so the buffer stores stay; there they are non-temporal WITHOUT the write-through bit.
+    // The chunk offset rides as the scalar offset; as a vector offset (one v_or per store) the shared-a / c streams lose 1 %:
+    // 6.44 / 6.42 / 6.33 -> 6.37 / 6.36 / 6.30 TB/s at D = 512 / 2048 / 4096 (profiles/r03/rows_store_issue_ab.log).
 #pragma unroll
-            for (int k = 0; k < K; ++k) st16<true>(q + k * 64, E::pack(r[k]));
-            return;
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        if constexpr (WHVI_FUSED_STORE_FORM == 1)        // A/B: the chunk offset in the VECTOR offset (one v_or per store)
-            uniform_st16<NT, !(SHARED_SRC && WHVI_FUSED_SHARED_PLAIN_NT)>(dst + base, tile_bytes, lane + k * 64, 0, E::pack(r[k]));
-        else
-            uniform_st16<NT, !(SHARED_SRC && WHVI_FUSED_SHARED_PLAIN_NT)>(dst + base, tile_bytes, lane, k * 1024, E::pack(r[k]));
-    }
+    for (int k = 0; k < K; ++k) uniform_st16<NT, !SHARED_SRC>(dst + base, tile_bytes, lane, k * 1024, E::pack(r[k]));
 }
 
 // Rows shorter than one 16-byte chunk (D = 1, 2 for f32; D = 1 for f64): one thread per row, same

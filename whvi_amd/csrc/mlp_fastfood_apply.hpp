@@ -85,9 +85,9 @@ __device__ __forceinline__ void mlp_ff_layer(float (&h)[R][MlpGeom<LOG2D>::C][4]
     typedef float f4 __attribute__((ext_vector_type(4)));
     float (&t)[K][4] = reinterpret_cast<float (&)[K][4]>(h);          // chunk (r, j) = tile chunk k = r C + j
     mlp_ff_scale<LOG2D, R>(h, lop, col);
-    fwht_tile<float, 4, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, true, 0>(t, lane);
+    fwht_tile<float, 4, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, 0>(t, lane);
     mlp_ff_scale<LOG2D, R>(h, lop + D, col);
-    fwht_tile<float, 4, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, true, SIGN_MID>(t, lane);
+    fwht_tile<float, 4, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, SIGN_MID>(t, lane);
 #pragma unroll
     for (int j = 0; j < C; ++j) {
         const uint32_t q = col + j * L;

@@ -72,8 +72,8 @@ __device__ __forceinline__ void mlp_ff_fwht(float (&h)[R][MlpGeom<LOG2D>::C][4],
     constexpr int SIGN_MID = fwht_sign_out<4, LOG2D>(0);
     static_assert(fwht_sign_out<4, LOG2D>(SIGN_MID) == 0, "two transforms restore the sign convention");
     float (&t)[K][4] = reinterpret_cast<float (&)[K][4]>(h);          // chunk (r, j) = tile chunk k = r C + j
-    if constexpr (FIRST) fwht_tile<float, 4, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, true, 0>(t, lane);
-    else fwht_tile<float, 4, K, LOG2D, POLICY_DPP, WHVI_FUSED_PKMASK, true, SIGN_MID>(t, lane);
+    if constexpr (FIRST) fwht_tile<float, 4, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, 0>(t, lane);
+    else fwht_tile<float, 4, K, LOG2D, POLICY_DPP, FUSED_PKMASK, true, SIGN_MID>(t, lane);
 }
 
 // mlp_ff_layer out of place, keeping both transforms: t1 = H(s2 hin) (sign convention SIGN_MID), t2 = H(g_k t1),
