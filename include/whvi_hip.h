@@ -292,6 +292,41 @@ int whvi_fused_shs_stacked_f32(void *dst, const void *src, const void *a, const 
                                int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
                                int32_t log2d, int32_t flags, void *stream);
 
+/* Backward of whvi_fused_shs_stacked_f32 in ONE launch plus a tiny finishing launch inside the same call.  float32.  Rows as
+ * there.  Per row, for j = 0 .. n_blocks - 1, the chain of whvi_fused_shs_bwd_f32 on segment j of grad_y
+ * (gy_j = grad_y[r, j * D : (j + 1) * D]):
+ *     t1 = H(c_j x);  u = H(b_js t1), grad_a[j] += gy_j u;  v = H(a_j gy_j), grad_b[j, s] += v t1;
+ *     w = H(b_js v), grad_c[j] += w x;  gx = c_0 w (j = 0), gx = gx + c_j w (j > 0: product and add are separate roundings)
+ *   grad_x : (n_samples * sample_stride, D), stored once per row after the last j, or NULL to skip the store: bit for bit the
+ *            grad_x of whvi_fused_shs_bwd_f32 per block, added in ascending j.
+ *   grad_a, grad_c : (n_blocks, D);  grad_b : (n_blocks, n_samples, D).  Block j's three are, bit for bit, what
+ *            whvi_fused_shs_bwd_f32 returns for a contiguous copy of segment j of grad_y with a[j], b[j], c[j]: the same
+ *            operands, tiles, fused multiply-adds, per-block partials and finishing order (ascending block).  No atomics:
+ *            bit-identical on every run.
+ *   grad_y : (n_samples * sample_stride, n_blocks * D).  x : (n_samples * sample_stride, D), or with flags =
+ *            WHVI_FUSED_SRC_SHARED (sample_stride, D): row r of every sample reads x[r] (grad_x is still written per
+ *            (sample, row): the caller sums over samples).
+ *   a, c : (n_blocks, D);  b : (n_blocks, n_samples, D).
+ *   work   : whvi_fused_shs_stacked_bwd_workspace(n_samples, sample_stride, log2d, n_blocks) bytes = n_blocks times
+ *            whvi_fused_shs_bwd_workspace(n_samples, sample_stride, log2d): one slot of 12 * D * n_blocks bytes per block of the
+ *            launch, the grid being that call's.  The query needs no device and depends on its arguments alone.  0 when
+ *            n_samples * sample_stride == 0; WHVI_ERR_ARG for a negative size, WHVI_ERR_SIZE outside the range.
+ * A row of x and its n_blocks segments of grad_y are read once and grad_x is written once: (2 + n_blocks) * D elements per row.
+ * Supported: 2 <= n_blocks <= 4 for 6 <= log2d <= 10, n_blocks = 2 at log2d = 11 -- whvi_fused_shs_stacked_bwd_supported(log2d,
+ * n_blocks) returns 1 exactly then (no device needed), the call WHVI_ERR_SIZE otherwise (n_blocks = 1 is
+ * whvi_fused_shs_bwd_f32), as it does when n_samples * sample_stride >= 2^32 or n_blocks * (n_samples + 2) * D >= 2^31.  flags
+ * other than 0 / WHVI_FUSED_SRC_SHARED, a negative size, a null pointer other than grad_x: WHVI_ERR_ARG; a pointer that is not
+ * 16-byte aligned: WHVI_ERR_ALIGN; grad_x, a parameter gradient or the workspace overlapping an input: WHVI_ERR_OVERLAP.
+ * n_samples * sample_stride == 0 returns WHVI_OK without a launch or a write.  Every argument check runs before any device
+ * call.  No allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_shs_stacked_bwd_kernel<float, log2d, K, n_blocks, NT>. */
+int     whvi_fused_shs_stacked_bwd_supported(int32_t log2d, int64_t n_blocks);
+int64_t whvi_fused_shs_stacked_bwd_workspace(int64_t n_samples, int64_t sample_stride, int32_t log2d, int64_t n_blocks);
+int     whvi_fused_shs_stacked_bwd_f32(void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                                       const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                                       int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                                       int32_t log2d, int32_t flags, void *stream);
+
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample
  * (src/weights.py:82-83,92), and kl_diag_normal(g_mu, g_sigma, 0, lambda) (src/weights.py:52-64,

@@ -131,6 +131,12 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_stacked_supported.argtypes = [i32, i64]
     lib.whvi_fused_shs_stacked_f32.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_f32.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
+    lib.whvi_fused_shs_stacked_bwd_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_bwd_supported.argtypes = [i32, i64]
+    lib.whvi_fused_shs_stacked_bwd_workspace.restype = i64
+    lib.whvi_fused_shs_stacked_bwd_workspace.argtypes = [i64, i64, i32, i64]
+    lib.whvi_fused_shs_stacked_bwd_f32.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -483,6 +489,67 @@ def fused_shs_stacked(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: to
                                               d.bit_length() - 1, FUSED_SRC_SHARED if shared else 0, _stream(src))
     _check(rc, "whvi_fused_shs_stacked")
     return out
+
+
+def fused_shs_stacked_bwd_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """Shapes the one-launch backward of the rectangular fastfood layer covers (``whvi_fused_shs_stacked_bwd_supported``,
+    restated: no library needed): float32, 2 <= ``n_blocks`` <= 4 for 64 <= D <= 1024 and ``n_blocks`` = 2 at D = 2048."""
+    if dtype != torch.float32 or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return (64 <= d <= 1024 and 2 <= n_blocks <= 4) or (d == 2048 and n_blocks == 2)
+
+
+def fused_shs_stacked_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                          n_samples: int, sample_stride: int, shared: bool = False, need_x: bool = True, grad_x: torch.Tensor = None):
+    """Backward of ``fused_shs_stacked`` in one call (whvi_fused_shs_stacked_bwd_f32): ``(grad_x | None, grad_a (J, D), grad_b
+    (J, S, D), grad_c (J, D))`` from ``grad_y`` ``(S * sample_stride, J * D)`` in (sample, row) order and the forward's operands
+    ``x`` ``(S * sample_stride, D)``, ``a, c`` ``(J, D)``, ``b`` ``(J, S, D)``.  ``shared``: ``x`` is ``(sample_stride, D)``, read
+    by every sample; ``grad_x`` still has ``S * sample_stride`` rows (the caller sums over samples).  ``need_x=False`` allocates
+    and writes no ``grad_x``; ``grad_x``: a contiguous, 16-byte aligned ``(S * sample_stride, D)`` float32 tensor to write instead
+    of a new one.  Block ``j``'s parameter gradients have the bits of ``fused_shs_bwd`` on the contiguous segment ``j`` of
+    ``grad_y``, ``grad_x`` those of the per-block ``grad_x`` added in ascending ``j``.  The workspace comes from torch's
+    allocator, sized by ``whvi_fused_shs_stacked_bwd_workspace``."""
+    S, stride = int(n_samples), int(sample_stride)
+    if grad_y.device.type != "cuda" or grad_y.dim() != 2:
+        raise RuntimeError("fused_shs_stacked_bwd: grad_y must be a 2-D CUDA tensor")
+    _require_f32_on_one_device("fused_shs_stacked_bwd", grad_y.device, (grad_y, x, a, b, c))
+    if a.dim() != 2 or x.dim() != 2:
+        raise RuntimeError("fused_shs_stacked_bwd: a must be (n_blocks, D) and x 2-D")
+    J, d = a.shape
+    if not fused_shs_stacked_bwd_supported(torch.float32, d, J):
+        raise RuntimeError(f"fused_shs_stacked_bwd: {J} blocks of {d} elements are outside the supported range "
+                           "(2 .. 4 blocks for 64 <= D <= 1024, 2 blocks at D = 2048)")
+    rows = S * stride
+    if (tuple(grad_y.shape) != (rows, J * d) or tuple(x.shape) != ((stride if shared else rows), d) or tuple(c.shape) != (J, d)
+            or tuple(b.shape) != (J, S, d)):
+        raise RuntimeError("fused_shs_stacked_bwd: operand shapes do not match (grad_y (n_samples * sample_stride, J * D); x the "
+                           "same rows of D, or sample_stride rows when shared; a, c (J, D); b (J, S, D))")
+    grad_y, x, a, b, c = (_aligned(t) for t in (grad_y, x, a, b, c))
+    dev = grad_y.device
+    if not need_x:
+        grad_x = None
+    elif grad_x is None:
+        grad_x = torch.empty((rows, d), dtype=torch.float32, device=dev)
+    elif not grad_x.is_contiguous() or tuple(grad_x.shape) != (rows, d) or grad_x.dtype != torch.float32 or grad_x.device != dev:
+        raise RuntimeError("fused_shs_stacked_bwd: bad grad_x tensor")
+    grad_a = torch.empty((J, d), dtype=torch.float32, device=dev)
+    grad_b = torch.empty((J, S, d), dtype=torch.float32, device=dev)
+    grad_c = torch.empty((J, d), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return grad_x, grad_a.zero_(), grad_b.zero_(), grad_c.zero_()
+    L = lib()
+    log2d = d.bit_length() - 1
+    n = int(L.whvi_fused_shs_stacked_bwd_workspace(S, stride, log2d, J))
+    if n < 0:
+        raise RuntimeError(f"whvi_fused_shs_stacked_bwd_workspace failed (code {n})")
+    work = torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+    with _OnDevice(dev):
+        rc = L.whvi_fused_shs_stacked_bwd_f32(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(),
+                                              grad_c.data_ptr(), work.data_ptr(), grad_y.data_ptr(), x.data_ptr(), a.data_ptr(),
+                                              b.data_ptr(), c.data_ptr(), J, S, stride, log2d, FUSED_SRC_SHARED if shared else 0,
+                                              _stream(grad_y))
+    _check(rc, "whvi_fused_shs_stacked_bwd")
+    return grad_x, grad_a, grad_b, grad_c
 
 
 def reparam_kl(g_mu: torch.Tensor, g_rho: torch.Tensor, eps: torch.Tensor, lambda_: float):

@@ -26,7 +26,8 @@ sums, ``grad_x`` rounded once) instead of two float32 upcasts and the float32 ch
 Rectangular layers (``WHVIFastfoodStackedMatrix``, ``WHVILinear(..., mode="fastfood_stacked")``): the paper's stacking -- the
 input zero-padded to ``D = 2^ceil(log2 n_in)``, ``J = ceil(n_out / D)`` independent square operators applied to it, their
 outputs concatenated and the surplus columns dropped.  On the GPU the float32 forward is ONE launch of
-``whvi_fused_shs_stacked_f32`` that reads a row once and writes all ``J`` blocks side by side.
+``whvi_fused_shs_stacked_f32`` that reads a row once and writes all ``J`` blocks side by side, and with
+``fused_backward = True`` the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f32``.
 """
 import torch
 import torch.nn as nn
@@ -279,7 +280,15 @@ class FastfoodStackedFunction(torch.autograd.Function):
     covers -- the row read once, ``J`` segments written -- and otherwise (host tensors, other dtypes, D < 64 or D > 2048, more
     blocks than fit the launch's LDS) the concatenation of ``FastfoodFunction``'s forward per block, which block ``j`` of the
     launch equals bit for bit.  Backward: per block, what ``FastfoodFunction.backward`` runs on that block's columns of
-    ``grad_y`` (``keep_half`` and ``fused_backward`` as there); the blocks' ``grad_x`` add up.  First order only."""
+    ``grad_y`` (``keep_half`` and ``fused_backward`` as there); the blocks' ``grad_x`` add up.  First order only.
+
+    ``fused_backward`` without ``keep_half`` (float32 tensors on ``x``'s device, rows == n_samples * sample_stride, at least one
+    of ``a, b, c`` wanting a gradient, 2 <= J <= 4 for 64 <= D <= 1024 or J = 2 at D = 2048 --
+    ``_hip.fused_shs_stacked_bwd_supported``): the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f32`` for all blocks
+    -- ``x`` and the ``J`` segments of ``grad_y`` read once, ``grad_x`` written once, no copy of a segment, no per-block
+    ``grad_x`` and no running sum.  Every gradient has the bits of the per-block loop with the flag set.  A shared
+    ``x`` that wants a gradient keeps the loop (the launch adds the blocks before the samples, the loop the samples before the
+    blocks); so does everything else -- ``J = 1``, ``J > 4``, D = 4096, host tensors, other dtypes, the flag off."""
 
     @staticmethod
     def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False):
@@ -300,6 +309,19 @@ class FastfoodStackedFunction(torch.autograd.Function):
         x, a, b, c = ctx.saved_tensors
         J, D = a.shape
         need_x, need_a, need_b, need_c = ctx.needs_input_grad[:4]
+        S, stride = ctx.n_samples, ctx.sample_stride
+        if (ctx.fused_backward and not ctx.keep_half and (need_a or need_b or need_c) and not (ctx.shared and need_x)
+                and all(t.dtype == torch.float32 and t.device == x.device for t in (x, grad_y, a, b, c))
+                and grad_y.size(0) == S * stride):
+            from whvi_amd import _hip
+            if _hip.fused_shs_stacked_bwd_supported(torch.float32, D, J):
+                # ONE launch for all J blocks: x and the J segments of grad_y read once, grad_x written once.  (A shared x that
+                # wants a gradient stays below: the launch adds the blocks per (sample, row) and the samples would be folded
+                # afterwards, where the loop folds each block's samples first -- the same sum in another order, not the same bits.)
+                grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_stacked_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
+                                                                            need_x=need_x)
+                return (grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None,
+                        None, None, None, None, None)
         blocks = grad_y.view(grad_y.size(0), J, D)
         grad_x, per_block = None, []
         for j in range(J):
@@ -319,7 +341,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     (dimensions: ``WHVIStackedMatrix.setup_dimensions``).  Parameters ``weight_matrices.<j>.{s1, s2, g_mu, g_rho}`` (+ optional
     ``bias`` (1, D_out)) -- the checkpoint keys and the creation order of ``WHVIStackedMatrix``, so its state dict loads and the
     same seed gives the same parameters."""
-    fused_backward = False    # as on WHVIFastfoodMatrix: True = each block's backward is one launch where FastfoodFunction's is
+    fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
     keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (per-block launches)
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
