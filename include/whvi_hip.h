@@ -184,6 +184,10 @@ int whvi_fused_shs_f64(void *dst, const void *src, const void *a, const void *b,
  * sample with WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM -- one transform per sample instead of two, the same
  * multiplies and butterflies in the same order, hence the same bits as the two-transform launch. */
 #define WHVI_FUSED_ONE_TRANSFORM 8
+/* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32 only; every other entry refuses them as unknown
+ * flags): an nn.ReLU in front of / behind the layer, applied on load / before the store -- max(., 0), NaN passing. */
+#define WHVI_FUSED_RELU_IN      16
+#define WHVI_FUSED_RELU_OUT     32
 
 int whvi_fused_shs_ex_f32(void *dst, const void *src, const void *a, const void *b,
                           const void *c, int64_t rows, int32_t log2d, int64_t n_samples,
@@ -291,6 +295,32 @@ int whvi_fused_shs_stacked_supported(int32_t log2d, int64_t n_blocks);
 int whvi_fused_shs_stacked_f32(void *dst, const void *src, const void *a, const void *b, const void *c,
                                int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
                                int32_t log2d, int32_t flags, void *stream);
+
+/* whvi_fused_shs_stacked_f32 with what a network puts around the layer folded into the same launch: the activation in front,
+ * the bias, the activation behind, and the narrowing to n_cols columns at a row pitch of the caller's.  float32.  Rows, src, a,
+ * b, c as there.  For col = j * D + n < n_cols:
+ *     dst[r * ld_dst + col] = act_out(a[j, n] * H(b[j, s, :] (.) H(c[j, :] (.) act_in(src_row)))[n] + bias[col])
+ *   act_in / act_out : max(., 0) with NaN passing, as torch.relu (WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT), else the identity.
+ *   bias  : (n_blocks * D) floats, or NULL: the add is a rounding of its own behind the a multiply, and is skipped -- not
+ *           "+ 0" -- without a bias.
+ *   dst   : n_samples * sample_stride rows of pitch ld_dst floats.  Columns n_cols .. ld_dst - 1 of every row, and everything
+ *           outside the rows, are not written.  n_cols and ld_dst are multiples of 4, (n_blocks - 1) * D < n_cols <=
+ *           n_blocks * D (the narrowing ends in the last block) and ld_dst >= n_cols.
+ * With bias == NULL, flags 0 / WHVI_FUSED_SRC_SHARED and n_cols == ld_dst == n_blocks * D the result is, bit for bit, that of
+ * whvi_fused_shs_stacked_f32.  A row is read once and n_cols columns are written.
+ * Supported: 6 <= log2d <= 11, n_blocks >= 1 and (12 + 4 * has_bias) * D * n_blocks <= 65536 (the bias is staged in LDS with the
+ * triples) -- whvi_fused_shs_stacked_layer_supported(log2d, n_blocks, has_bias) returns 1 exactly then (no device needed), the
+ * call WHVI_ERR_SIZE otherwise, as it does for an n_cols or ld_dst outside the rule above and when n_samples * sample_stride >=
+ * 2^32.  Unknown flags, a negative size, a null pointer other than bias: WHVI_ERR_ARG; a pointer that is not 16-byte aligned:
+ * WHVI_ERR_ALIGN; the rows * ld_dst floats of dst overlapping any input, the bias included: WHVI_ERR_OVERLAP.  n_samples *
+ * sample_stride == 0 returns WHVI_OK without a launch.  Every argument check runs before any device call, in
+ * whvi_fused_shs_stacked_f32's order.  No atomics, no allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_shs_stacked_layer_kernel<float, log2d, K, NT>. */
+int whvi_fused_shs_stacked_layer_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias);
+int whvi_fused_shs_stacked_layer_f32(void *dst, const void *src, const void *a, const void *b, const void *c,
+                                     const void *bias /* (n_blocks * D) floats or NULL */,
+                                     int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                     int64_t n_cols, int64_t ld_dst, int32_t flags, void *stream);
 
 /* Backward of whvi_fused_shs_stacked_f32 in ONE launch plus a tiny finishing launch inside the same call.  float32.  Rows as
  * there.  Per row, for j = 0 .. n_blocks - 1, the chain of whvi_fused_shs_bwd_f32 on segment j of grad_y

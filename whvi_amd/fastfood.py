@@ -27,7 +27,10 @@ Rectangular layers (``WHVIFastfoodStackedMatrix``, ``WHVILinear(..., mode="fastf
 input zero-padded to ``D = 2^ceil(log2 n_in)``, ``J = ceil(n_out / D)`` independent square operators applied to it, their
 outputs concatenated and the surplus columns dropped.  On the GPU the float32 forward is ONE launch of
 ``whvi_fused_shs_stacked_f32`` that reads a row once and writes all ``J`` blocks side by side, and with
-``fused_backward = True`` the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f32``.
+``fused_backward = True`` the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f32``.  With
+``fused_epilogue = True`` the bias, an ``nn.ReLU`` in front of / behind the layer (``WHVINetwork.forward_batched``) and the
+narrowing to an ``n_out`` that is a multiple of 4 are part of that forward launch, ``whvi_fused_shs_stacked_layer_f32``, instead
+of passes of their own over the ``(S, batch, J D)`` activations; all three flags default to False.
 """
 import torch
 import torch.nn as nn
@@ -36,7 +39,8 @@ from torch.autograd.function import once_differentiable
 
 from whvi_amd.utils import is_pow_of_2
 
-__all__ = ["FastfoodFunction", "WHVIFastfoodMatrix", "FastfoodStackedFunction", "WHVIFastfoodStackedMatrix"]
+__all__ = ["FastfoodFunction", "WHVIFastfoodMatrix", "FastfoodStackedFunction", "FastfoodStackedLayerFunction",
+           "WHVIFastfoodStackedMatrix"]
 
 
 def _fwht(x):
@@ -272,6 +276,36 @@ class WHVIFastfoodMatrix(nn.Module):
         return out
 
 
+def _fastfood_stacked_backward(grad_y, x, a, b, c, S, stride, shared, keep_half, fused_backward, needs):
+    """``(grad_x, grad_a, grad_b, grad_c)`` of ``y[:, j * D:(j + 1) * D] = a[j] * fwht(b[j, s] * fwht(c[j] * x))`` -- the backward of
+    ``FastfoodStackedFunction`` (its docstring describes the routes), also run by ``FastfoodStackedLayerFunction`` behind its
+    masks.  ``keep_half`` / ``fused_backward``: the flags as the forward resolved them; ``needs``: which of ``x, a, b, c`` want a
+    gradient (the others come back as None)."""
+    J, D = a.shape
+    need_x, need_a, need_b, need_c = needs
+    if (fused_backward and not keep_half and (need_a or need_b or need_c) and not (shared and need_x)
+            and all(t.dtype == torch.float32 and t.device == x.device for t in (x, grad_y, a, b, c))
+            and grad_y.size(0) == S * stride):
+        from whvi_amd import _hip
+        if _hip.fused_shs_stacked_bwd_supported(torch.float32, D, J):
+            # ONE launch for all J blocks: x and the J segments of grad_y read once, grad_x written once.  (A shared x that
+            # wants a gradient stays below: the launch adds the blocks per (sample, row) and the samples would be folded
+            # afterwards, where the loop folds each block's samples first -- the same sum in another order, not the same bits.)
+            grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_stacked_bwd(grad_y, x, a, b, c, S, stride, shared=shared, need_x=need_x)
+            return grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None
+    blocks = grad_y.view(grad_y.size(0), J, D)
+    grad_x, per_block = None, []
+    for j in range(J):
+        gx, ga, gb, gc = _fastfood_backward(blocks[:, j].contiguous(), x, a[j], b[j], c[j], S, stride, shared, keep_half,
+                                            fused_backward, (need_x, need_a, need_b, need_c))
+        if gx is not None:
+            grad_x = gx if grad_x is None else grad_x + gx
+        per_block.append((ga, gb, gc))
+    grad_a, grad_b, grad_c = (torch.stack([g[i] for g in per_block]) if need else None
+                              for i, need in enumerate((need_a, need_b, need_c)))
+    return grad_x, grad_a, grad_b, grad_c
+
+
 class FastfoodStackedFunction(torch.autograd.Function):
     """``y[:, j * D:(j + 1) * D] = a[j] * fwht(b[j, s] * fwht(c[j] * x))`` for ``j = 0 .. J - 1``: ``J`` square fastfood operators
     on the same rows ``(n_samples, rows_per_sample, D)`` flattened, side by side.  ``a, c``: (J, D); ``b``: (J, S, D).
@@ -307,32 +341,50 @@ class FastfoodStackedFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, grad_y):
         x, a, b, c = ctx.saved_tensors
-        J, D = a.shape
-        need_x, need_a, need_b, need_c = ctx.needs_input_grad[:4]
-        S, stride = ctx.n_samples, ctx.sample_stride
-        if (ctx.fused_backward and not ctx.keep_half and (need_a or need_b or need_c) and not (ctx.shared and need_x)
-                and all(t.dtype == torch.float32 and t.device == x.device for t in (x, grad_y, a, b, c))
-                and grad_y.size(0) == S * stride):
-            from whvi_amd import _hip
-            if _hip.fused_shs_stacked_bwd_supported(torch.float32, D, J):
-                # ONE launch for all J blocks: x and the J segments of grad_y read once, grad_x written once.  (A shared x that
-                # wants a gradient stays below: the launch adds the blocks per (sample, row) and the samples would be folded
-                # afterwards, where the loop folds each block's samples first -- the same sum in another order, not the same bits.)
-                grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_stacked_bwd(grad_y, x, a, b, c, S, stride, shared=ctx.shared,
-                                                                            need_x=need_x)
-                return (grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None,
-                        None, None, None, None, None)
-        blocks = grad_y.view(grad_y.size(0), J, D)
-        grad_x, per_block = None, []
-        for j in range(J):
-            gx, ga, gb, gc = _fastfood_backward(blocks[:, j].contiguous(), x, a[j], b[j], c[j], ctx.n_samples, ctx.sample_stride,
-                                                ctx.shared, ctx.keep_half, ctx.fused_backward, (need_x, need_a, need_b, need_c))
-            if gx is not None:
-                grad_x = gx if grad_x is None else grad_x + gx
-            per_block.append((ga, gb, gc))
-        grad_a, grad_b, grad_c = (torch.stack([g[i] for g in per_block]) if need else None
-                                  for i, need in enumerate((need_a, need_b, need_c)))
-        return grad_x, grad_a, grad_b, grad_c, None, None, None, None, None
+        grads = _fastfood_stacked_backward(grad_y, x, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half,
+                                           ctx.fused_backward, ctx.needs_input_grad[:4])
+        return (*grads, None, None, None, None, None)
+
+
+class FastfoodStackedLayerFunction(torch.autograd.Function):
+    """``y = act_out(FastfoodStackedFunction(act_in(x), a, b, c) + bias)[:, :n_cols]`` in ONE launch of
+    ``whvi_fused_shs_stacked_layer_f32``: float32 CUDA tensors that ``_hip.fused_shs_stacked_layer_supported``
+    covers, ``bias`` of ``J * D`` elements or None, ``n_cols`` a multiple of 4 in ``((J - 1) D, J D]``, ``act_in`` / ``act_out``
+    ``torch.relu`` with ``relu_in`` / ``relu_out``.  The values are those of the separate passes, bit for bit.
+
+    Backward: composed from what exists -- the mask of ``relu_out`` from the saved output (saved only then), the bias gradient
+    as the row sum, the gradient zero-padded to ``J * D`` columns, ``act_in(x)`` recomputed, ``FastfoodStackedFunction``'s
+    backward (``fused_backward`` as there), and the mask of ``relu_in`` on ``grad_x``: the same operands in the same launches as
+    the separate passes' autograd graph.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, c, bias, n_cols, relu_in, relu_out, n_samples, sample_stride, shared=False, fused_backward=False):
+        from whvi_amd import _hip
+        ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
+        ctx.relu_in, ctx.relu_out, ctx.fused_backward = bool(relu_in), bool(relu_out), bool(fused_backward)
+        y = _hip.fused_shs_stacked_layer(x, a, b, c, ctx.n_samples, ctx.sample_stride, bias=bias, n_cols=n_cols, relu_in=ctx.relu_in,
+                                         relu_out=ctx.relu_out, shared=ctx.shared)
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.save_for_backward(x, a, b, c, y if ctx.relu_out else None)     # (the activation's mask comes from its own output)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, a, b, c, y = ctx.saved_tensors
+        full = a.numel()                                                   # J * D
+        g = (torch.ops.aten.threshold_backward(grad_y, y, 0) if ctx.relu_out else grad_y).contiguous()
+        grad_bias = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[4]:
+            grad_bias = F.pad(g.sum(dim=0), (0, full - g.size(1))).view(ctx.bias_shape)
+        if g.size(1) < full:
+            g = F.pad(g, (0, full - g.size(1)))
+        xin = torch.relu(x) if ctx.relu_in else x
+        grad_x, grad_a, grad_b, grad_c = _fastfood_stacked_backward(g, xin, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared,
+                                                                    False, ctx.fused_backward, ctx.needs_input_grad[:4])
+        if ctx.relu_in and grad_x is not None:
+            grad_x = torch.ops.aten.threshold_backward(grad_x, xin, 0)
+        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None
 
 
 class WHVIFastfoodStackedMatrix(nn.Module):
@@ -343,6 +395,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     same seed gives the same parameters."""
     fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
     keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (per-block launches)
+    fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
         super().__init__()
@@ -360,9 +413,25 @@ class WHVIFastfoodStackedMatrix(nn.Module):
         """(stack, D_in) tensor of one per-block vector."""
         return torch.stack([getattr(m, name) for m in self.weight_matrices])
 
-    def forward_mc(self, x, n_samples):
+    def fuses_relu(self, x):
+        """True when ``forward_mc(x, ..., relu_in=, relu_out=)`` folds the activations (and the bias and the narrowing) into its
+        one launch: ``fused_epilogue`` set, float32 ``x`` and parameters on one CUDA device (so ``keep_half`` does not apply) and
+        a ``(D_in, stack, bias)`` the launch covers.  Otherwise they are separate ``torch.relu`` passes -- same values either way."""
+        if not self.fused_epilogue or x.device.type != "cuda" or x.dtype != torch.float32:
+            return False
+        if any(p.dtype != torch.float32 or p.device != x.device for p in self.parameters()):
+            return False
+        from whvi_amd import _hip
+        return _hip.fused_shs_stacked_layer_supported(torch.float32, self.D_in, self.stack, self.bias is not None)
+
+    def forward_mc(self, x, n_samples, relu_in=False, relu_out=False):
         """(batch, n_in) or (n_samples, batch, n_in) -> (n_samples, batch, n_out); sample k of block j uses row ``[j, k]`` of
-        one ``randn(stack, n_samples, D_in)`` draw."""
+        one ``randn(stack, n_samples, D_in)`` draw.  ``relu_in`` / ``relu_out``: ``relu(layer(relu(x)))``, folded into the launch
+        where ``fuses_relu(x)``."""
+        fold = self.fuses_relu(x)
+        if (relu_in or relu_out) and not fold:
+            out = self.forward_mc(torch.relu(x) if relu_in else x, n_samples)
+            return torch.relu(out) if relu_out else out
         s1, s2, g_mu = self._stacked("s1"), self._stacked("s2"), self._stacked("g_mu")
         eps = torch.randn(self.stack, n_samples, self.D_in, device=g_mu.device)
         g = g_mu.unsqueeze(1) + F.softplus(self._stacked("g_rho")).unsqueeze(1) * eps                 # (J, S, D)
@@ -375,6 +444,14 @@ class WHVIFastfoodStackedMatrix(nn.Module):
         shared = x.dim() == 2                  # a (batch, D) input shared by all samples: read by every sample, never expanded
         batch = x.size(0) if shared else x.size(1)
         rows = x.contiguous() if shared else x.reshape(n_samples * batch, self.D_in).contiguous()
+        narrow = self.n_out < self.D_out and self.n_out % 4 == 0
+        if fold and (self.bias is not None or relu_in or relu_out or narrow):
+            # ONE launch with the epilogue: no pass for the bias, none for a ReLU, and n_out columns written at pitch n_out where
+            # that is a multiple of 4 (otherwise pitch D_out and the narrowing view, as below)
+            n_cols = self.n_out if self.n_out % 4 == 0 else self.D_out
+            out = FastfoodStackedLayerFunction.apply(rows, s1, g, s2, self.bias, n_cols, relu_in, relu_out, n_samples, batch, shared,
+                                                     self.fused_backward).view(n_samples, batch, n_cols)
+            return out if n_cols == self.n_out else out[..., :self.n_out]
         out = FastfoodStackedFunction.apply(rows, s1, g, s2, n_samples, batch, shared, half, self.fused_backward)
         out = out.view(n_samples, batch, self.D_out)        # (the launch always writes pitch D_out)
         if self.bias is not None:
