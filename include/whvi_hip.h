@@ -184,8 +184,9 @@ int whvi_fused_shs_f64(void *dst, const void *src, const void *a, const void *b,
  * sample with WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM -- one transform per sample instead of two, the same
  * multiplies and butterflies in the same order, hence the same bits as the two-transform launch. */
 #define WHVI_FUSED_ONE_TRANSFORM 8
-/* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32 only; every other entry refuses them as unknown
- * flags): an nn.ReLU in front of / behind the layer, applied on load / before the store -- max(., 0), NaN passing. */
+/* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32 and its backward,
+ * whvi_fused_shs_stacked_layer_bwd_f32, only; every other entry refuses them as unknown flags): an nn.ReLU in front of / behind
+ * the layer, applied on load / before the store -- max(., 0), NaN passing; in the backward, the masks of those two. */
 #define WHVI_FUSED_RELU_IN      16
 #define WHVI_FUSED_RELU_OUT     32
 
@@ -356,6 +357,45 @@ int     whvi_fused_shs_stacked_bwd_f32(void *grad_x, void *grad_a, void *grad_b,
                                        const void *grad_y, const void *x, const void *a, const void *b, const void *c,
                                        int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
                                        int32_t log2d, int32_t flags, void *stream);
+
+/* Backward of whvi_fused_shs_stacked_layer_f32 in ONE launch plus a tiny finishing launch inside the same call: the call above
+ * with the layer's epilogue folded in -- the masks of both ReLUs, the zero padding past n_cols and the bias sum.  float32.
+ * Per row, for j = 0 .. n_blocks - 1 and col = j * D + n:
+ *     xin    = WHVI_FUSED_RELU_IN ? max(x, 0) (NaN passing) : x
+ *     g_j[n] = 0 for col >= n_cols (those 16-byte chunks of grad_y and y are not read), elsewhere
+ *              WHVI_FUSED_RELU_OUT ? (y[col] <= 0 ? +0 : grad_y[col]) : grad_y[col]   -- a select, aten.threshold_backward:
+ *              a NaN y passes grad_y, y = -0 gives 0, a NaN grad_y under y <= 0 gives 0
+ *     grad_bias[col] += g_j[n];  the chain of whvi_fused_shs_stacked_bwd_f32 on (xin, g_j), the zero chunks included
+ *     grad_x = WHVI_FUSED_RELU_IN ? (xin <= 0 ? +0 : gx) : gx, stored once per row, or not at all with grad_x == NULL
+ *   grad_y, y : (n_samples * sample_stride, n_cols) at a common row pitch of ld floats; columns n_cols .. ld - 1 are never
+ *            read.  y (the forward's output) is given exactly with WHVI_FUSED_RELU_OUT and NULL otherwise.
+ *   x, a, b, c, grad_a, grad_b, grad_c : as in whvi_fused_shs_stacked_bwd_f32.
+ *   grad_bias : (n_blocks * D) floats or NULL (no sum at all); all n_blocks * D entries are written, those from n_cols on as +0.
+ *   work   : whvi_fused_shs_stacked_layer_bwd_workspace(n_samples, sample_stride, log2d, n_blocks, has_bias) bytes: one slot of
+ *            (12 + 4 * has_bias) * D * n_blocks bytes per block of the launch (the grid of whvi_fused_shs_bwd_f32).  0 when
+ *            n_samples * sample_stride == 0; WHVI_ERR_ARG for a negative size, WHVI_ERR_SIZE outside the range.
+ * grad_x, grad_a, grad_b, grad_c are, bit for bit, whvi_fused_shs_stacked_bwd_f32 on the masked, zero-padded g and on
+ * relu(x), followed by the mask on grad_x.  grad_bias is each lane's plain float sum in tile order, then the reductions of
+ * grad_a (same-column butterfly, wave order, ascending block): deterministic, its own summation order.  No atomics.
+ * Supported: 2 <= n_blocks <= 4 for 6 <= log2d <= 10, n_blocks = 2 at log2d = 11, with or without a bias --
+ * whvi_fused_shs_stacked_layer_bwd_supported(log2d, n_blocks, has_bias) returns 1 exactly then (no device needed).  Checks, all
+ * before any device call: flags outside WHVI_FUSED_SRC_SHARED | WHVI_FUSED_RELU_IN | WHVI_FUSED_RELU_OUT or a negative size
+ * WHVI_ERR_ARG; an unsupported (log2d, n_blocks, has_bias), n_cols or ld not a multiple of 4, n_cols outside
+ * ((n_blocks - 1) * D, n_blocks * D], ld < n_cols or ld >= 2^32 WHVI_ERR_SIZE; n_samples * sample_stride == 0 WHVI_OK without a launch or a
+ * write; a null pointer other than grad_x / grad_bias, a null y with WHVI_FUSED_RELU_OUT, a y without it WHVI_ERR_ARG;
+ * n_samples * sample_stride >= 2^32, rows * ld > 2^60 or n_blocks * (n_samples + 2 + has_bias) * D >= 2^31 WHVI_ERR_SIZE; a misaligned pointer
+ * WHVI_ERR_ALIGN; an output or the workspace overlapping an input (rows * ld floats for grad_y and y) WHVI_ERR_OVERLAP.  No
+ * allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_shs_stacked_layer_bwd_kernel<float, log2d, K, n_blocks, has_bias, NT>. */
+int     whvi_fused_shs_stacked_layer_bwd_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias);
+int64_t whvi_fused_shs_stacked_layer_bwd_workspace(int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                                   int64_t n_blocks, int32_t has_bias);
+int     whvi_fused_shs_stacked_layer_bwd_f32(void *grad_x /* or NULL */, void *grad_a, void *grad_b, void *grad_c,
+                                             void *grad_bias /* (n_blocks * D) floats or NULL */, void *work,
+                                             const void *grad_y, const void *y /* NULL unless WHVI_FUSED_RELU_OUT */,
+                                             const void *x, const void *a, const void *b, const void *c,
+                                             int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                             int64_t n_cols, int64_t ld, int32_t flags, void *stream);
 
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample

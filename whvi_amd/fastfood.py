@@ -355,13 +355,25 @@ class FastfoodStackedLayerFunction(torch.autograd.Function):
     Backward: composed from what exists -- the mask of ``relu_out`` from the saved output (saved only then), the bias gradient
     as the row sum, the gradient zero-padded to ``J * D`` columns, ``act_in(x)`` recomputed, ``FastfoodStackedFunction``'s
     backward (``fused_backward`` as there), and the mask of ``relu_in`` on ``grad_x``: the same operands in the same launches as
-    the separate passes' autograd graph.  First order only."""
+    the separate passes' autograd graph.  First order only.
+
+    ``fused_epilogue_backward`` AND ``fused_backward`` (float32 tensors on one CUDA device, rows == n_samples * sample_stride, at
+    least one of ``a, b, c, bias`` wanting a gradient, ``x`` not a shared input that itself wants a gradient, a ``(D, J, bias)``
+    that ``_hip.fused_shs_stacked_layer_bwd_supported`` covers, and a mask or a padding to fold -- ``relu_in``, ``relu_out`` or
+    ``n_cols < J * D``; with nothing but the bias sum the launch measured no faster than the row sum and the launch it starts
+    from, so that case stays composed): the backward is ONE launch of
+    ``whvi_fused_shs_stacked_layer_bwd_f32`` -- both masks, the zero padding and the bias sum inside it, so the
+    masked gradient, its padded copy, ``act_in(x)`` and the unmasked ``grad_x`` are never materialised.  ``grad_x`` and the
+    gradients of ``a, b, c`` have the bits of the composed backward with ``fused_backward`` set; the bias gradient is the same
+    sum in another (deterministic) order, which is why this is a flag of its own.  Everything else runs the composed backward."""
 
     @staticmethod
-    def forward(ctx, x, a, b, c, bias, n_cols, relu_in, relu_out, n_samples, sample_stride, shared=False, fused_backward=False):
+    def forward(ctx, x, a, b, c, bias, n_cols, relu_in, relu_out, n_samples, sample_stride, shared=False, fused_backward=False,
+                fused_epilogue_backward=False):
         from whvi_amd import _hip
         ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
         ctx.relu_in, ctx.relu_out, ctx.fused_backward = bool(relu_in), bool(relu_out), bool(fused_backward)
+        ctx.fused_epilogue_backward = bool(fused_epilogue_backward)
         y = _hip.fused_shs_stacked_layer(x, a, b, c, ctx.n_samples, ctx.sample_stride, bias=bias, n_cols=n_cols, relu_in=ctx.relu_in,
                                          relu_out=ctx.relu_out, shared=ctx.shared)
         ctx.bias_shape = None if bias is None else bias.shape
@@ -373,6 +385,26 @@ class FastfoodStackedLayerFunction(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, a, b, c, y = ctx.saved_tensors
         full = a.numel()                                                   # J * D
+        need_x, need_a, need_b, need_c, need_bias = ctx.needs_input_grad[:5]
+        need_bias = need_bias and ctx.bias_shape is not None
+        S, stride = ctx.n_samples, ctx.sample_stride
+        # a mask or the padding to fold: with the bias sum alone the launch measured no faster
+        folds = ctx.relu_in or ctx.relu_out or grad_y.size(1) < full
+        if (ctx.fused_epilogue_backward and ctx.fused_backward and folds and (need_a or need_b or need_c or need_bias)
+                and not (ctx.shared and need_x) and grad_y.size(0) == S * stride
+                and all(t.dtype == torch.float32 and t.device == x.device and t.device.type == "cuda"
+                        for t in (x, grad_y, a, b, c) + ((y,) if ctx.relu_out else ()))):
+            from whvi_amd import _hip
+            if _hip.fused_shs_stacked_layer_bwd_supported(torch.float32, a.size(1), a.size(0), need_bias):
+                # ONE launch: the masks, the padding and the bias sum inside it (a shared x that wants a gradient stays
+                # below for _fastfood_stacked_backward's reason)
+                if ctx.relu_out and grad_y.size(0) > 1 and grad_y.stride(0) != y.stride(0):
+                    grad_y = grad_y.contiguous()       # (a view of a wider gradient, e.g. behind torch.cat: y's pitch is n_cols)
+                grad_x, grad_a, grad_b, grad_c, grad_bias = _hip.fused_shs_stacked_layer_bwd(
+                    grad_y, y, x, a, b, c, S, stride, n_cols=grad_y.size(1), relu_in=ctx.relu_in, relu_out=ctx.relu_out,
+                    shared=ctx.shared, need_x=need_x, need_bias=need_bias)
+                return (grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None,
+                        grad_bias.view(ctx.bias_shape) if need_bias else None, None, None, None, None, None, None, None, None)
         g = (torch.ops.aten.threshold_backward(grad_y, y, 0) if ctx.relu_out else grad_y).contiguous()
         grad_bias = None
         if ctx.bias_shape is not None and ctx.needs_input_grad[4]:
@@ -384,7 +416,7 @@ class FastfoodStackedLayerFunction(torch.autograd.Function):
                                                                     False, ctx.fused_backward, ctx.needs_input_grad[:4])
         if ctx.relu_in and grad_x is not None:
             grad_x = torch.ops.aten.threshold_backward(grad_x, xin, 0)
-        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None
+        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None
 
 
 class WHVIFastfoodStackedMatrix(nn.Module):
@@ -396,6 +428,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
     keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (per-block launches)
     fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
+    fused_epilogue_backward = False    # True (with fused_backward and fused_epilogue) = the backward of that launch is one launch too, with both masks and the bias sum folded in (float32, where _hip.fused_shs_stacked_layer_bwd_supported and a ReLU or a narrowing is folded); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
         super().__init__()
@@ -450,7 +483,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
             # that is a multiple of 4 (otherwise pitch D_out and the narrowing view, as below)
             n_cols = self.n_out if self.n_out % 4 == 0 else self.D_out
             out = FastfoodStackedLayerFunction.apply(rows, s1, g, s2, self.bias, n_cols, relu_in, relu_out, n_samples, batch, shared,
-                                                     self.fused_backward).view(n_samples, batch, n_cols)
+                                                     self.fused_backward, self.fused_epilogue_backward).view(n_samples, batch, n_cols)
             return out if n_cols == self.n_out else out[..., :self.n_out]
         out = FastfoodStackedFunction.apply(rows, s1, g, s2, n_samples, batch, shared, half, self.fused_backward)
         out = out.view(n_samples, batch, self.D_out)        # (the launch always writes pitch D_out)
