@@ -297,6 +297,27 @@ int whvi_fused_shs_stacked_f32(void *dst, const void *src, const void *a, const 
                                int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
                                int32_t log2d, int32_t flags, void *stream);
 
+/* whvi_fused_shs_stacked_f32 for 16-bit ACTIVATION storage: dst and src are float16 (_f16) or bfloat16 (_bf16), a, b, c stay
+ * float32 -- the contract of whvi_fused_shs_ex_f16 / _bf16: the input is upcast exactly, every multiply is its own float32
+ * rounding, the butterflies are float32, and each element is rounded to 16 bits ONCE, when it is stored.  Shapes, row order
+ * and flags as above.  Block j of dst is, element for element, whvi_fused_shs_ex_f16 / _bf16(src, a[j], b[j], c[j], axis =
+ * WHVI_AXIS_COL) -- with WHVI_FUSED_SRC_SHARED, that entry on the source repeated n_samples times (it has no shared-source
+ * form) -- non-finite inputs included, the sign of an exact zero exempt.  A row is read once and n_blocks segments are written:
+ * (1 + n_blocks) * D * 2 bytes per row.
+ * Supported: whvi_fused_shs_stacked_f32's rule, 6 <= log2d <= 11, n_blocks >= 1 and 12 * D * n_blocks <= 65536 (the staged
+ * vectors are float32) -- whvi_fused_shs_stacked16_supported(log2d, n_blocks) returns 1 exactly then (no device needed).  The
+ * same checks in the same order and with the same codes as whvi_fused_shs_stacked_f32, the overlap check on byte extents of
+ * 2-byte activations and 4-byte vectors, all before any device call; n_samples * sample_stride == 0 returns WHVI_OK without a
+ * launch.  No atomics, no allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_stacked16_kernel<__half | __hip_bfloat16, log2d, K, NT>. */
+int whvi_fused_shs_stacked16_supported(int32_t log2d, int64_t n_blocks);
+int whvi_fused_shs_stacked_f16(void *dst, const void *src, const void *a, const void *b, const void *c,
+                               int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                               int32_t log2d, int32_t flags, void *stream);
+int whvi_fused_shs_stacked_bf16(void *dst, const void *src, const void *a, const void *b, const void *c,
+                                int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                                int32_t log2d, int32_t flags, void *stream);
+
 /* whvi_fused_shs_stacked_f32 with what a network puts around the layer folded into the same launch: the activation in front,
  * the bias, the activation behind, and the narrowing to n_cols columns at a row pitch of the caller's.  float32.  Rows, src, a,
  * b, c as there.  For col = j * D + n < n_cols:

@@ -131,6 +131,11 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_stacked_supported.argtypes = [i32, i64]
     lib.whvi_fused_shs_stacked_f32.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_f32.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
+    lib.whvi_fused_shs_stacked16_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked16_supported.argtypes = [i32, i64]
+    for fn in (lib.whvi_fused_shs_stacked_f16, lib.whvi_fused_shs_stacked_bf16):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
     lib.whvi_fused_shs_stacked_layer_supported.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_layer_supported.argtypes = [i32, i64, i32]
     lib.whvi_fused_shs_stacked_layer_f32.restype = ctypes.c_int
@@ -500,6 +505,52 @@ def fused_shs_stacked(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: to
         rc = lib().whvi_fused_shs_stacked_f32(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride,
                                               d.bit_length() - 1, FUSED_SRC_SHARED if shared else 0, _stream(src))
     _check(rc, "whvi_fused_shs_stacked")
+    return out
+
+
+def fused_shs_stacked16_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """Shapes the one-launch rectangular fastfood layer covers on 16-bit activations (``whvi_fused_shs_stacked16_supported``,
+    restated: no library needed): float16 / bfloat16, and ``fused_shs_stacked_supported``'s rule for the float32 vectors --
+    64 <= D <= 2048 and ``n_blocks >= 1`` triples of ``D`` floats within 64 KiB of LDS."""
+    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return 64 <= d <= 2048 and n_blocks >= 1 and 12 * d * n_blocks <= 65536
+
+
+def fused_shs_stacked16(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int, sample_stride: int,
+                        shared: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """``fused_shs_stacked`` for float16 / bfloat16 ``src`` with float32 ``a, c`` ``(J, D)`` and ``b`` ``(J, n_samples, D)``
+    (whvi_fused_shs_stacked_f16 / _bf16): float32 arithmetic on the exactly-upcast input, the result in ``src``'s dtype,
+    rounded ONCE when it is stored.  Block ``j`` has the bits of ``fused_shs(src, a[j], b[j], c[j])`` -- with ``shared``
+    (``src`` ``(sample_stride, D)``, read by every sample) of that launch on ``src.repeat(n_samples, 1)``.  ``out``: a
+    contiguous, 16-byte aligned ``(n_samples * sample_stride, J * D)`` tensor of ``src``'s dtype to write instead of a new one."""
+    S, stride = int(n_samples), int(sample_stride)
+    if src.device.type != "cuda" or src.dim() != 2 or src.dtype not in _HALF_DTYPES:
+        raise RuntimeError("fused_shs_stacked16: src must be a 2-D float16 / bfloat16 CUDA tensor")
+    _require_f32_on_one_device("fused_shs_stacked16 (16-bit activations: a, b, c)", src.device, (a, b, c))
+    d = src.size(1)
+    if a.dim() != 2 or a.size(1) != d:
+        raise RuntimeError("fused_shs_stacked16: a must be (n_blocks, D)")
+    J = a.size(0)
+    if not fused_shs_stacked16_supported(src.dtype, d, J):
+        raise RuntimeError(f"fused_shs_stacked16: {J} blocks of {d} elements are outside the supported range "
+                           "(64 <= D <= 2048, 12 * D * n_blocks <= 65536)")
+    rows = S * stride
+    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d):
+        raise RuntimeError("fused_shs_stacked16: operand shapes do not match (src rows must be n_samples * sample_stride, or "
+                           "sample_stride when shared; a, c (J, D); b (J, S, D))")
+    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
+    if out is None:
+        out = torch.empty((rows, J * d), dtype=src.dtype, device=src.device)
+    elif not out.is_contiguous() or tuple(out.shape) != (rows, J * d) or out.dtype != src.dtype or out.device != src.device:
+        raise RuntimeError("fused_shs_stacked16: bad out tensor")
+    if rows == 0:
+        return out
+    fn = getattr(lib(), "whvi_fused_shs_stacked_" + _DTYPE_SUFFIX[src.dtype])
+    with _OnDevice(src.device):
+        rc = fn(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride, d.bit_length() - 1,
+                FUSED_SRC_SHARED if shared else 0, _stream(src))
+    _check(rc, "whvi_fused_shs_stacked16")
     return out
 
 

@@ -1,5 +1,6 @@
 // whvi_amd/csrc/abi.hip -- dtype-independent part of the C ABI (include/whvi_hip.h).
 #include "dispatch.hpp"
+#include "fused_stacked16.hpp"
 
 namespace whvi {
 
@@ -66,6 +67,55 @@ extern "C" __attribute__((visibility("default"))) int whvi_max_log2d(int32_t dty
     case WHVI_I32: return max_log2d<int32_t>();
     default: return -1;
     }
+}
+
+// ---- the rectangular fastfood layer on 16-bit activations (fused_stacked16.hpp): the support rule and the argument checks,
+// shared by fused_stacked_f16.hip and fused_stacked_bf16.hip
+namespace whvi {
+
+// whvi_fused_shs_stacked_f32's checks in its order, with byte extents of 2-byte activations and 4-byte vectors
+int fused_stacked16_check(FusedStackedArgs &r, bool &launch, void *dst, const void *src, const void *a, const void *b,
+                          const void *c, int64_t J, int64_t S, int64_t stride, int32_t log2d, int32_t flags)
+{
+    g_err[0] = 0;
+    launch = false;
+    if (flags & ~WHVI_FUSED_SRC_SHARED)
+        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: unknown fused flags%s 0x%llx (0 or the shared-source flag)", "", flags);
+    if (J < 0 || S < 0 || stride < 0) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: negative size%s", "");
+    if (log2d < FUSED_STACKED_MIN_LOG2D || log2d > FUSED_STACKED_MAX_LOG2D)
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: log2(D)%s = %lld is outside the supported range [6, %lld]", "", log2d,
+                    FUSED_STACKED_MAX_LOG2D);
+    if (!fused_stacked16_supported(log2d, J))
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: %s%lld blocks need 12 D bytes of LDS each, at most %lld fit 64 KiB", "",
+                    J, FUSED_STACKED_LDS_BYTES / ((int64_t)12 << log2d));
+    if (S == 0 || stride == 0) return WHVI_OK;
+    if (!dst || !src || !a || !b || !c) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: null pointer%s", "");
+    if (S >= ((int64_t)1 << 32) / stride)
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: rows are indexed with 32 bits%s", "");
+    if (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15)
+        return fail(WHVI_ERR_ALIGN, "whvi_fused_shs_stacked16: a pointer%s is not 16-byte aligned", "");
+    const FusedBwdGeom geom = fused_bwd_geom(S, stride, log2d);
+    if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: too many blocks%s", "");
+    const int64_t row_bytes = (int64_t)2 << log2d, vec_bytes = (int64_t)4 << log2d, rows = S * stride;
+    const bool shared = (flags & WHVI_FUSED_SRC_SHARED) != 0;
+    const struct { const void *p; int64_t bytes; } ins[] = {
+        {src, (shared ? stride : rows) * row_bytes}, {a, J * vec_bytes}, {b, J * S * vec_bytes}, {c, J * vec_bytes}};
+    for (const auto &t : ins)
+        if (ranges_overlap(dst, rows * J * row_bytes, t.p, t.bytes))
+            return fail(WHVI_ERR_OVERLAP, "whvi_fused_shs_stacked16: dst overlaps an input%s", "");
+    r.dst = dst, r.src = src, r.a = a, r.b = b, r.c = c;
+    r.n_blocks = J, r.n_samples = S, r.sample_stride = stride, r.log2d = log2d, r.src_shared = shared, r.geom = geom;
+    // the streamed bytes: the J output segments, and the source unless it is shared
+    r.nt = rows * row_bytes * (J + (shared ? 0 : 1)) > NT_MIN_BYTES;
+    launch = true;
+    return WHVI_OK;
+}
+
+}  // namespace whvi
+
+extern "C" __attribute__((visibility("default"))) int whvi_fused_shs_stacked16_supported(int32_t log2d, int64_t n_blocks)
+{
+    return fused_stacked16_supported(log2d, n_blocks) ? 1 : 0;
 }
 
 // per-dtype implementations live in fwht_<dtype>.hip

@@ -30,7 +30,9 @@ outputs concatenated and the surplus columns dropped.  On the GPU the float32 fo
 ``fused_backward = True`` the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f32``.  With
 ``fused_epilogue = True`` the bias, an ``nn.ReLU`` in front of / behind the layer (``WHVINetwork.forward_batched``) and the
 narrowing to an ``n_out`` that is a multiple of 4 are part of that forward launch, ``whvi_fused_shs_stacked_layer_f32``, instead
-of passes of their own over the ``(S, batch, J D)`` activations; all three flags default to False.
+of passes of their own over the ``(S, batch, J D)`` activations; all three flags default to False.  With
+``keep_half = True`` a float16 / bfloat16 input takes ONE launch of ``whvi_fused_shs_stacked_f16 / _bf16`` over the same range
+ and the output keeps its dtype; its backward stays per block and its epilogue stays separate passes.
 """
 import torch
 import torch.nn as nn
@@ -313,7 +315,10 @@ class FastfoodStackedFunction(torch.autograd.Function):
     Forward: ONE launch of ``whvi_fused_shs_stacked_f32`` for float32 CUDA tensors that ``_hip.fused_shs_stacked_supported``
     covers -- the row read once, ``J`` segments written -- and otherwise (host tensors, other dtypes, D < 64 or D > 2048, more
     blocks than fit the launch's LDS) the concatenation of ``FastfoodFunction``'s forward per block, which block ``j`` of the
-    launch equals bit for bit.  Backward: per block, what ``FastfoodFunction.backward`` runs on that block's columns of
+    launch equals bit for bit.  ``keep_half`` (float16 / bfloat16 CUDA ``x``, float32 ``a, b, c`` on its device, a ``(D, J)`` that
+    ``_hip.fused_shs_stacked16_supported`` covers -- the float32 launch's range): ONE launch of ``whvi_fused_shs_stacked_f16 /
+    _bf16``, the output in ``x``'s dtype and block ``j`` the bits of ``FastfoodFunction``'s 16-bit forward; outside
+    that range the per-block 16-bit launches and their concatenation.  Backward: per block, what ``FastfoodFunction.backward`` runs on that block's columns of
     ``grad_y`` (``keep_half`` and ``fused_backward`` as there); the blocks' ``grad_x`` add up.  First order only.
 
     ``fused_backward`` without ``keep_half`` (float32 tensors on ``x``'s device, rows == n_samples * sample_stride, at least one
@@ -334,6 +339,11 @@ class FastfoodStackedFunction(torch.autograd.Function):
             from whvi_amd import _hip
             if _hip.fused_shs_stacked_supported(torch.float32, x.size(1), a.size(0)):
                 return _hip.fused_shs_stacked(x, a, b, c, ctx.n_samples, ctx.sample_stride, shared=ctx.shared)
+        if ctx.keep_half and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c)):
+            from whvi_amd import _hip
+            if _hip.fused_shs_stacked16_supported(x.dtype, x.size(1), a.size(0)):
+                # 16-bit activations: ONE launch as well, each block's bits those of its 16-bit launch below
+                return _hip.fused_shs_stacked16(x, a, b, c, ctx.n_samples, ctx.sample_stride, shared=ctx.shared)
         return torch.cat([_pipeline(x, a[j], b[j], c[j], ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half)
                           for j in range(a.size(0))], dim=1)
 
@@ -426,7 +436,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     ``bias`` (1, D_out)) -- the checkpoint keys and the creation order of ``WHVIStackedMatrix``, so its state dict loads and the
     same seed gives the same parameters."""
     fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
-    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (per-block launches)
+    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (forward: one launch for all blocks where _hip.fused_shs_stacked16_supported, per-block launches elsewhere; backward: per block; the epilogue is never folded)
     fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
     fused_epilogue_backward = False    # True (with fused_backward and fused_epilogue) = the backward of that launch is one launch too, with both masks and the bias sum folded in (float32, where _hip.fused_shs_stacked_layer_bwd_supported and a ReLU or a narrowing is folded); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
 
