@@ -379,6 +379,31 @@ int     whvi_fused_shs_stacked_bwd_f32(void *grad_x, void *grad_a, void *grad_b,
                                        int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
                                        int32_t log2d, int32_t flags, void *stream);
 
+/* Backward of whvi_fused_shs_stacked_f16 / _bf16 in ONE launch plus a tiny finishing launch inside the same call: the call above
+ * on 16-bit activation streams.  grad_y, x and grad_x are __half / __hip_bfloat16; a, b, c, grad_a, grad_b, grad_c and work are
+ * float32.  The chain above runs in float32 on the exactly-upcast x and grad_y; gx stays float32 across the n_blocks segments
+ * and grad_x is rounded to 16 bits ONCE, when it is stored after the last j: whvi_fused_shs_stacked_bwd_f32 on the upcasts,
+ * cast once (the per-block launches of whvi_fused_shs_bwd_f16 / _bf16 added in 16 bits round 2 * n_blocks - 1 times).  Block
+ * j's grad_a, grad_b, grad_c are, bit for bit, what whvi_fused_shs_bwd_f16 / _bf16 returns for a contiguous copy of segment j of
+ * grad_y with a[j], b[j], c[j], and from log2d = 9 up the float32 call's on the upcasts.  No atomics: bit-identical on every
+ * run.  Shapes, flags and the workspace (whvi_fused_shs_stacked_bwd_workspace, unchanged: the grid and the slots are the
+ * same) as above; (2 + n_blocks) * D * 2 bytes per row.
+ * Supported: the float32 call's rule, 2 <= n_blocks <= 4 for 6 <= log2d <= 10, n_blocks = 2 at log2d = 11 --
+ * whvi_fused_shs_stacked_bwd16_supported(log2d, n_blocks) returns 1 exactly then (no device needed).  The same checks in the
+ * same order and with the same codes as whvi_fused_shs_stacked_bwd_f32, the overlap check on byte extents of 2-byte
+ * activations and 4-byte vectors, all before any device call; n_samples * sample_stride == 0 returns WHVI_OK without a launch
+ * or a write.  No allocation, no synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_stacked_bwd16_kernel<__half | __hip_bfloat16, log2d, K, n_blocks, NT>. */
+int whvi_fused_shs_stacked_bwd16_supported(int32_t log2d, int64_t n_blocks);
+int whvi_fused_shs_stacked_bwd_f16(void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                                   const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                                   int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                                   int32_t log2d, int32_t flags, void *stream);
+int whvi_fused_shs_stacked_bwd_bf16(void *grad_x, void *grad_a, void *grad_b, void *grad_c, void *work,
+                                    const void *grad_y, const void *x, const void *a, const void *b, const void *c,
+                                    int64_t n_blocks, int64_t n_samples, int64_t sample_stride,
+                                    int32_t log2d, int32_t flags, void *stream);
+
 /* Backward of whvi_fused_shs_stacked_layer_f32 in ONE launch plus a tiny finishing launch inside the same call: the call above
  * with the layer's epilogue folded in -- the masks of both ReLUs, the zero padding past n_cols and the bias sum.  float32.
  * Per row, for j = 0 .. n_blocks - 1 and col = j * D + n:

@@ -6,6 +6,7 @@ forward runs outside the timed region), a warm-up of 30 backward passes per rout
 the repeats; median and min-max per route.  The yardstick is the per-block route of the same run.
 
     python tools/fastfood_stacked_bwd_rate.py --out profiles/r15/fastfood_stacked_bwd_rate.json
+    python tools/fastfood_stacked_bwd_rate.py --dtype float16 --dtype bfloat16 --all-pairs --out profiles/r19/fastfood_stacked_bwd16_rate.json
 
 Routes: ``launch`` (the flag on); ``per_block_fused`` (the flag on with ``_hip.fused_shs_stacked_bwd_supported`` answering no: the
 loop over the blocks, each block one launch of whvi_fused_shs_bwd_f32 -- the route every shape took before the launch existed
@@ -17,7 +18,15 @@ held before the backward.  ``TBps`` of the launch is (2 + J) activations -- x an
 Shapes (D, J, samples, batch, shared x): (1024, 4, 16, 8192) with an input of its own and with a shared one; (128, 4, 64, 1000);
 (2048, 2, 16, 4096); one small shape (1024, 4, 1, 256), where a launch cannot fill the chip.  All of x, a, b, c want a gradient,
 except at the shared shape: a shared x that wants a gradient keeps the loop on every route (FastfoodStackedFunction), so there
-x is data -- a network's first layer -- and a, b, c want theirs."""
+x is data -- a network's first layer -- and a, b, c want theirs.
+
+``--dtype float16 | bfloat16`` (repeatable; tools/fused_bwd_rate.py is the model): the same shapes on 16-bit activations with
+float32 a, b, c -- whvi_fused_shs_stacked_bwd_f16 / _bf16, DESIGN 5.2k.  ``launch``: ``keep_half``, ``fused_backward`` and
+``fused_backward16``; ``per_block_fused``: the same flags with ``_hip.fused_shs_stacked_bwd16_supported`` answering no -- the loop
+of whvi_fused_shs_bwd_f16 / _bf16 launches, the route before the launch existed; ``per_block_chain``: ``keep_half`` alone;
+``copy_probe``: (2 + J) * D * 2 bytes per row.  ``--all-pairs`` adds one shape per shipped (D, J), 16 samples of 2^23 / D rows
+with an input of its own, so that every pair of the support rule has its own verdict: a pair stays in the Python rule if the
+launch's median is below the per-block route's in the same run."""
 import argparse
 import json
 import os
@@ -32,32 +41,42 @@ from whvi_amd.fastfood import FastfoodStackedFunction  # noqa: E402
 
 SHAPES = ((1024, 4, 16, 8192, False), (1024, 4, 16, 8192, True), (128, 4, 64, 1000, False), (2048, 2, 16, 4096, False),
           (1024, 4, 1, 256, False))
-ROUTES = {"launch": (True, True), "per_block_fused": (True, False), "per_block_chain": (False, False)}   # (flag, launch allowed)
-_SUPPORTED = _hip.fused_shs_stacked_bwd_supported
+# route -> ((keep_half, fused_backward, fused_backward16), launch allowed)
+ROUTES32 = {"launch": ((False, True, False), True), "per_block_fused": ((False, True, False), False),
+            "per_block_chain": ((False, False, False), False)}
+ROUTES16 = {"launch": ((True, True, True), True), "per_block_fused": ((True, True, True), False),
+            "per_block_chain": ((True, False, False), False)}
+ALL_PAIRS = tuple((1 << L, J, 16, (1 << 23) >> L, False) for L in range(6, 11) for J in (2, 3, 4)) + ((2048, 2, 16, 4096, False),)
+DTYPES = {"float32": torch.float32, "float16": torch.float16, "bfloat16": torch.bfloat16}
 
 
-def one_shape(d, J, S, batch, shared, repeats, warmup):
+def one_shape(d, J, S, batch, shared, repeats, warmup, dtype=torch.float32):
     dev = torch.device("cuda", 0)
     rows = S * batch
+    half = dtype != torch.float32
+    esize = 2 if half else 4
+    ROUTES = ROUTES16 if half else ROUTES32
+    query = "fused_shs_stacked_bwd16_supported" if half else "fused_shs_stacked_bwd_supported"
+    _SUPPORTED = getattr(_hip, query)
     g = torch.Generator(device=dev).manual_seed(d + J)
-    x = torch.randn(batch if shared else rows, d, device=dev, generator=g).requires_grad_(not shared)
-    gy = torch.randn(rows, J * d, device=dev, generator=g)
+    x = torch.randn(batch if shared else rows, d, device=dev, generator=g).to(dtype).requires_grad_(not shared)
+    gy = torch.randn(rows, J * d, device=dev, generator=g).to(dtype)
     a = torch.randn(J, d, device=dev, generator=g).mul_(0.01).requires_grad_()
     c = torch.randn(J, d, device=dev, generator=g).mul_(0.01).requires_grad_()
     b = torch.randn(J, S, d, device=dev, generator=g).requires_grad_()
     wanted = (a, b, c) if shared else (x, a, b, c)
-    act = 4.0 * rows * d
-    probe_src = torch.empty((2 + J) * rows * d * 2, dtype=torch.uint8, device=dev).random_()
+    act = float(esize) * rows * d
+    probe_src = torch.empty((2 + J) * rows * d * esize // 2, dtype=torch.uint8, device=dev).random_()
     probe_dst = torch.empty_like(probe_src)
     times = {name: [] for name in ROUTES}
     times["copy_probe"] = []
     kernels, peaks = {}, {}
 
     def backward(name, timed):
-        flag, allowed = ROUTES[name]
-        _hip.fused_shs_stacked_bwd_supported = _SUPPORTED if allowed else (lambda *args: False)
+        flags, allowed = ROUTES[name]
+        setattr(_hip, query, _SUPPORTED if allowed else (lambda *args: False))
         try:
-            y = FastfoodStackedFunction.apply(x, a, b, c, S, batch, shared, False, flag)
+            y = FastfoodStackedFunction.apply(x, a, b, c, S, batch, shared, *flags)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if timed == "peak":
                 torch.cuda.synchronize()
@@ -68,7 +87,7 @@ def one_shape(d, J, S, batch, shared, repeats, warmup):
             e1.record()
             e1.synchronize()
         finally:
-            _hip.fused_shs_stacked_bwd_supported = _SUPPORTED
+            setattr(_hip, query, _SUPPORTED)
         if timed == "peak":
             return torch.cuda.max_memory_allocated(dev) - held
         del grads
@@ -98,7 +117,7 @@ def one_shape(d, J, S, batch, shared, repeats, warmup):
         for name in ROUTES:                                         # alternating: one measurement of each route per repeat
             times[name].append(backward(name, "time"))
         times["copy_probe"].append(probe())
-    out = {"D": d, "n_blocks": J, "n_samples": S, "batch": batch, "rows": rows, "x_shared": shared, "x_wants_gradient": not shared,
+    out = {"dtype": str(dtype).replace("torch.", ""), "D": d, "n_blocks": J, "n_samples": S, "batch": batch, "rows": rows, "x_shared": shared, "x_wants_gradient": not shared,
            "activation_bytes": act, "kernels": kernels,
            "workspace_bytes": int(_hip.lib().whvi_fused_shs_stacked_bwd_workspace(S, batch, d.bit_length() - 1, J)), "routes": {}}
     for name, ts in times.items():
@@ -113,8 +132,8 @@ def one_shape(d, J, S, batch, shared, repeats, warmup):
     out["speedup_over_per_block_fused"] = pb["ms_median"] / f["ms_median"]
     out["speedup_over_per_block_chain"] = ch["ms_median"] / f["ms_median"]
     out["launch_max_below_per_block_fused_min"] = f["ms_max"] < pb["ms_min"]
-    print(f"D={d:5d} J={J} S={S:3d} B={batch:6d} shared={int(shared)}: launch {f['ms_median']:.3f} ms [{f['ms_min']:.3f}-{f['ms_max']:.3f}], "
-          f"peak {f['peak_activations']:.2f} A, {f['TBps_median']:.2f} TB/s at {4 * (2 + J)} D bytes per row; per-block fused "
+    print(f"{out['dtype']} D={d:5d} J={J} S={S:3d} B={batch:6d} shared={int(shared)}: launch {f['ms_median']:.3f} ms [{f['ms_min']:.3f}-{f['ms_max']:.3f}], "
+          f"peak {f['peak_activations']:.2f} A, {f['TBps_median']:.2f} TB/s at {esize * (2 + J)} D bytes per row; per-block fused "
           f"{pb['ms_median']:.3f} ms [{pb['ms_min']:.3f}-{pb['ms_max']:.3f}], peak {pb['peak_activations']:.2f} A; per-block chain "
           f"{ch['ms_median']:.3f} ms [{ch['ms_min']:.3f}-{ch['ms_max']:.3f}], peak {ch['peak_activations']:.2f} A; copy probe "
           f"{out['routes']['copy_probe']['ms_median']:.3f} ms; speedup {out['speedup_over_per_block_fused']:.2f} / "
@@ -128,10 +147,13 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=30)
+    ap.add_argument("--dtype", action="append", choices=sorted(DTYPES), default=None, help="repeatable; default float32")
+    ap.add_argument("--all-pairs", action="store_true", help="also one shape per shipped (D, J)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     assert args.repeats >= 9, "at least 9 alternating repeats"
-    results = [one_shape(*shape, args.repeats, args.warmup) for shape in SHAPES]
+    shapes = SHAPES + (ALL_PAIRS if args.all_pairs else ())
+    results = [one_shape(*shape, args.repeats, args.warmup, DTYPES[name]) for name in (args.dtype or ["float32"]) for shape in shapes]
     doc = {"tool": "tools/fastfood_stacked_bwd_rate.py", "argv": sys.argv[1:], "device": torch.cuda.get_device_name(0),
            "repeats": args.repeats, "warmup": args.warmup, "results": results}
     if args.out:

@@ -146,6 +146,11 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_stacked_bwd_workspace.argtypes = [i64, i64, i32, i64]
     lib.whvi_fused_shs_stacked_bwd_f32.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
+    lib.whvi_fused_shs_stacked_bwd16_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_bwd16_supported.argtypes = [i32, i64]
+    for fn in (lib.whvi_fused_shs_stacked_bwd_f16, lib.whvi_fused_shs_stacked_bwd_bf16):   # (16-bit: grad_x, grad_y and x)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i32, vp]
     lib.whvi_fused_shs_stacked_layer_bwd_supported.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_layer_bwd_supported.argtypes = [i32, i64, i32]
     lib.whvi_fused_shs_stacked_layer_bwd_workspace.restype = i64
@@ -668,6 +673,71 @@ def fused_shs_stacked_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor
                                               b.data_ptr(), c.data_ptr(), J, S, stride, log2d, FUSED_SRC_SHARED if shared else 0,
                                               _stream(grad_y))
     _check(rc, "whvi_fused_shs_stacked_bwd")
+    return grad_x, grad_a, grad_b, grad_c
+
+
+def fused_shs_stacked_bwd16_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """Shapes the one-launch backward of the rectangular fastfood layer covers on 16-bit activations
+    (``whvi_fused_shs_stacked_bwd16_supported``, restated: no library needed): float16 / bfloat16, and
+    ``fused_shs_stacked_bwd_supported``'s rule for the float32 vectors -- 2 <= ``n_blocks`` <= 4 for 64 <= D <= 1024 and
+    ``n_blocks`` = 2 at D = 2048."""
+    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return (64 <= d <= 1024 and 2 <= n_blocks <= 4) or (d == 2048 and n_blocks == 2)
+
+
+def fused_shs_stacked_bwd16(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                            n_samples: int, sample_stride: int, shared: bool = False, need_x: bool = True,
+                            grad_x: torch.Tensor = None):
+    """``fused_shs_stacked_bwd`` for float16 / bfloat16 ``grad_y`` and ``x`` of one dtype with float32 ``a, c`` ``(J, D)`` and
+    ``b`` ``(J, S, D)`` (whvi_fused_shs_stacked_bwd_f16 / _bf16): ``(grad_x | None, grad_a (J, D), grad_b (J, S, D), grad_c
+    (J, D))``, float32 arithmetic on the exactly-upcast values.  ``grad_x`` is in the activations' dtype and is rounded ONCE,
+    after the last block: the float32 launch's ``grad_x`` on the upcasts, cast.  Block ``j``'s float32 parameter gradients have
+    the bits of ``fused_shs_bwd`` (16-bit) on the contiguous segment ``j`` of ``grad_y``.  ``shared``, ``need_x``, ``grad_x``
+    (a contiguous, 16-byte aligned ``(S * sample_stride, D)`` tensor of that dtype): as in ``fused_shs_stacked_bwd``.  The
+    workspace comes from torch's allocator, sized by ``whvi_fused_shs_stacked_bwd_workspace``."""
+    S, stride = int(n_samples), int(sample_stride)
+    if grad_y.device.type != "cuda" or grad_y.dim() != 2 or grad_y.dtype not in _HALF_DTYPES:
+        raise RuntimeError("fused_shs_stacked_bwd16: grad_y must be a 2-D float16 / bfloat16 CUDA tensor")
+    act, dev = grad_y.dtype, grad_y.device
+    if x.dtype != act or x.device != dev:
+        raise RuntimeError("fused_shs_stacked_bwd16: grad_y and x must share one 16-bit dtype and device")
+    _require_f32_on_one_device("fused_shs_stacked_bwd16 (16-bit activations: a, b, c)", dev, (a, b, c))
+    if a.dim() != 2 or x.dim() != 2:
+        raise RuntimeError("fused_shs_stacked_bwd16: a must be (n_blocks, D) and x 2-D")
+    J, d = a.shape
+    if not fused_shs_stacked_bwd16_supported(act, d, J):
+        raise RuntimeError(f"fused_shs_stacked_bwd16: {J} blocks of {d} elements are outside the supported range "
+                           "(2 .. 4 blocks for 64 <= D <= 1024, 2 blocks at D = 2048)")
+    rows = S * stride
+    if (tuple(grad_y.shape) != (rows, J * d) or tuple(x.shape) != ((stride if shared else rows), d) or tuple(c.shape) != (J, d)
+            or tuple(b.shape) != (J, S, d)):
+        raise RuntimeError("fused_shs_stacked_bwd16: operand shapes do not match (grad_y (n_samples * sample_stride, J * D); x the "
+                           "same rows of D, or sample_stride rows when shared; a, c (J, D); b (J, S, D))")
+    grad_y, x, a, b, c = (_aligned(t) for t in (grad_y, x, a, b, c))
+    if not need_x:
+        grad_x = None
+    elif grad_x is None:
+        grad_x = torch.empty((rows, d), dtype=act, device=dev)
+    elif not grad_x.is_contiguous() or tuple(grad_x.shape) != (rows, d) or grad_x.dtype != act or grad_x.device != dev:
+        raise RuntimeError("fused_shs_stacked_bwd16: bad grad_x tensor")
+    grad_a = torch.empty((J, d), dtype=torch.float32, device=dev)
+    grad_b = torch.empty((J, S, d), dtype=torch.float32, device=dev)
+    grad_c = torch.empty((J, d), dtype=torch.float32, device=dev)
+    if rows == 0:
+        return grad_x, grad_a.zero_(), grad_b.zero_(), grad_c.zero_()
+    L = lib()
+    log2d = d.bit_length() - 1
+    n = int(L.whvi_fused_shs_stacked_bwd_workspace(S, stride, log2d, J))
+    if n < 0:
+        raise RuntimeError(f"whvi_fused_shs_stacked_bwd_workspace failed (code {n})")
+    work = torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+    fn = getattr(L, "whvi_fused_shs_stacked_bwd_" + _DTYPE_SUFFIX[act])
+    with _OnDevice(dev):
+        rc = fn(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(), grad_c.data_ptr(),
+                work.data_ptr(), grad_y.data_ptr(), x.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride, log2d,
+                FUSED_SRC_SHARED if shared else 0, _stream(grad_y))
+    _check(rc, "whvi_fused_shs_stacked_bwd16")
     return grad_x, grad_a, grad_b, grad_c
 
 

@@ -32,7 +32,9 @@ outputs concatenated and the surplus columns dropped.  On the GPU the float32 fo
 narrowing to an ``n_out`` that is a multiple of 4 are part of that forward launch, ``whvi_fused_shs_stacked_layer_f32``, instead
 of passes of their own over the ``(S, batch, J D)`` activations; all three flags default to False.  With
 ``keep_half = True`` a float16 / bfloat16 input takes ONE launch of ``whvi_fused_shs_stacked_f16 / _bf16`` over the same range
- and the output keeps its dtype; its backward stays per block and its epilogue stays separate passes.
+ and the output keeps its dtype; with ``fused_backward = True`` and ``fused_backward16 = True`` as well its backward
+is ONE launch of ``whvi_fused_shs_stacked_bwd_f16 / _bf16`` (``grad_x`` rounded once instead of once per block and
+once per add, which is why it is a flag of its own), per block otherwise; its epilogue stays separate passes.
 """
 import torch
 import torch.nn as nn
@@ -278,11 +280,11 @@ class WHVIFastfoodMatrix(nn.Module):
         return out
 
 
-def _fastfood_stacked_backward(grad_y, x, a, b, c, S, stride, shared, keep_half, fused_backward, needs):
+def _fastfood_stacked_backward(grad_y, x, a, b, c, S, stride, shared, keep_half, fused_backward, needs, fused_backward16=False):
     """``(grad_x, grad_a, grad_b, grad_c)`` of ``y[:, j * D:(j + 1) * D] = a[j] * fwht(b[j, s] * fwht(c[j] * x))`` -- the backward of
     ``FastfoodStackedFunction`` (its docstring describes the routes), also run by ``FastfoodStackedLayerFunction`` behind its
-    masks.  ``keep_half`` / ``fused_backward``: the flags as the forward resolved them; ``needs``: which of ``x, a, b, c`` want a
-    gradient (the others come back as None)."""
+    masks.  ``keep_half`` / ``fused_backward`` / ``fused_backward16``: the flags as the forward resolved them; ``needs``: which
+    of ``x, a, b, c`` want a gradient (the others come back as None)."""
     J, D = a.shape
     need_x, need_a, need_b, need_c = needs
     if (fused_backward and not keep_half and (need_a or need_b or need_c) and not (shared and need_x)
@@ -294,6 +296,16 @@ def _fastfood_stacked_backward(grad_y, x, a, b, c, S, stride, shared, keep_half,
             # wants a gradient stays below: the launch adds the blocks per (sample, row) and the samples would be folded
             # afterwards, where the loop folds each block's samples first -- the same sum in another order, not the same bits.)
             grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_stacked_bwd(grad_y, x, a, b, c, S, stride, shared=shared, need_x=need_x)
+            return grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None
+    if (keep_half and fused_backward and fused_backward16 and (need_a or need_b or need_c) and not (shared and need_x)
+            and x.dtype in _HALF and grad_y.dtype == x.dtype and grad_y.device == x.device
+            and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c)) and grad_y.size(0) == S * stride):
+        from whvi_amd import _hip
+        if _hip.fused_shs_stacked_bwd16_supported(x.dtype, D, J):
+            # ONE launch on the 16-bit streams: grad_x stays float32 across the blocks and is rounded once (the loop below rounds
+            # each block's grad_x and each add: other bits, hence the flag).  (A shared x that wants a gradient stays below: the
+            # per-sample 16-bit gradients would each be rounded before the fold over the samples.)
+            grad_x, grad_a, grad_b, grad_c = _hip.fused_shs_stacked_bwd16(grad_y, x, a, b, c, S, stride, shared=shared, need_x=need_x)
             return grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None
     blocks = grad_y.view(grad_y.size(0), J, D)
     grad_x, per_block = None, []
@@ -318,7 +330,7 @@ class FastfoodStackedFunction(torch.autograd.Function):
     launch equals bit for bit.  ``keep_half`` (float16 / bfloat16 CUDA ``x``, float32 ``a, b, c`` on its device, a ``(D, J)`` that
     ``_hip.fused_shs_stacked16_supported`` covers -- the float32 launch's range): ONE launch of ``whvi_fused_shs_stacked_f16 /
     _bf16``, the output in ``x``'s dtype and block ``j`` the bits of ``FastfoodFunction``'s 16-bit forward; outside
-    that range the per-block 16-bit launches and their concatenation.  Backward: per block, what ``FastfoodFunction.backward`` runs on that block's columns of
+    that range the per-block 16-bit launches and their concatenation.  Backward (unless a paragraph below applies): per block, what ``FastfoodFunction.backward`` runs on that block's columns of
     ``grad_y`` (``keep_half`` and ``fused_backward`` as there); the blocks' ``grad_x`` add up.  First order only.
 
     ``fused_backward`` without ``keep_half`` (float32 tensors on ``x``'s device, rows == n_samples * sample_stride, at least one
@@ -327,11 +339,21 @@ class FastfoodStackedFunction(torch.autograd.Function):
     -- ``x`` and the ``J`` segments of ``grad_y`` read once, ``grad_x`` written once, no copy of a segment, no per-block
     ``grad_x`` and no running sum.  Every gradient has the bits of the per-block loop with the flag set.  A shared
     ``x`` that wants a gradient keeps the loop (the launch adds the blocks before the samples, the loop the samples before the
-    blocks); so does everything else -- ``J = 1``, ``J > 4``, D = 4096, host tensors, other dtypes, the flag off."""
+    blocks); so does everything else -- ``J = 1``, ``J > 4``, D = 4096, host tensors, other dtypes, the flag off.
+
+    ``keep_half`` AND ``fused_backward`` AND ``fused_backward16`` (16-bit ``x`` and ``grad_y`` of one dtype, float32 ``a, b, c`` on
+    ``x``'s device, rows == n_samples * sample_stride, at least one of ``a, b, c`` wanting a gradient, ``x`` not a shared input
+    that itself wants a gradient, a ``(D, J)`` that ``_hip.fused_shs_stacked_bwd16_supported`` covers -- the float32 launch's
+    range): the backward is ONE launch of ``whvi_fused_shs_stacked_bwd_f16 / _bf16``.  The parameter gradients
+    have the bits of the per-block 16-bit launches; ``grad_x`` is accumulated in float32 and rounded ONCE, where the loop rounds
+    ``2 J - 1`` times, so its bits differ (it is the closer one) -- which is why this is a flag of its own.  Everything else
+    runs what it runs without the flag."""
 
     @staticmethod
-    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False):
+    def forward(ctx, x, a, b, c, n_samples, sample_stride, shared=False, keep_half=False, fused_backward=False,
+                fused_backward16=False):
         ctx.fused_backward = bool(fused_backward) and x.device.type == "cuda"
+        ctx.fused_backward16 = bool(fused_backward16) and x.device.type == "cuda"
         ctx.save_for_backward(x, a, b, c)
         ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
         ctx.keep_half = bool(keep_half) and x.device.type == "cuda" and x.dtype in _HALF
@@ -352,8 +374,8 @@ class FastfoodStackedFunction(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, a, b, c = ctx.saved_tensors
         grads = _fastfood_stacked_backward(grad_y, x, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared, ctx.keep_half,
-                                           ctx.fused_backward, ctx.needs_input_grad[:4])
-        return (*grads, None, None, None, None, None)
+                                           ctx.fused_backward, ctx.needs_input_grad[:4], fused_backward16=ctx.fused_backward16)
+        return (*grads, None, None, None, None, None, None)
 
 
 class FastfoodStackedLayerFunction(torch.autograd.Function):
@@ -434,9 +456,13 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     ``D_in = 2^ceil(log2 n_in)`` applied to the zero-padded input, their outputs concatenated and narrowed to ``n_out``
     (dimensions: ``WHVIStackedMatrix.setup_dimensions``).  Parameters ``weight_matrices.<j>.{s1, s2, g_mu, g_rho}`` (+ optional
     ``bias`` (1, D_out)) -- the checkpoint keys and the creation order of ``WHVIStackedMatrix``, so its state dict loads and the
-    same seed gives the same parameters."""
+    same seed gives the same parameters.  The flags below choose the launches (all default to False; ``FastfoodStackedFunction``
+    and ``FastfoodStackedLayerFunction`` describe the routes): on float16 / bfloat16 activations ``keep_half`` keeps them 16-bit
+    through one forward launch, and with ``fused_backward`` and ``fused_backward16`` as well the backward of all blocks is one
+    16-bit launch that rounds ``grad_x`` once."""
     fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
-    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (forward: one launch for all blocks where _hip.fused_shs_stacked16_supported, per-block launches elsewhere; backward: per block; the epilogue is never folded)
+    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (forward: one launch for all blocks where _hip.fused_shs_stacked16_supported, per-block launches elsewhere; backward: per block, or one launch with fused_backward16; the epilogue is never folded)
+    fused_backward16 = False  # True (with keep_half and fused_backward) = the 16-bit backward of all blocks is one launch (where _hip.fused_shs_stacked_bwd16_supported: FastfoodStackedFunction); grad_x is rounded once instead of 2 J - 1 times, so its bits differ from the per-block route's; the parameter gradients are bit-equal
     fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
     fused_epilogue_backward = False    # True (with fused_backward and fused_epilogue) = the backward of that launch is one launch too, with both masks and the bias sum folded in (float32, where _hip.fused_shs_stacked_layer_bwd_supported and a ReLU or a narrowing is folded); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
 
@@ -495,7 +521,8 @@ class WHVIFastfoodStackedMatrix(nn.Module):
             out = FastfoodStackedLayerFunction.apply(rows, s1, g, s2, self.bias, n_cols, relu_in, relu_out, n_samples, batch, shared,
                                                      self.fused_backward, self.fused_epilogue_backward).view(n_samples, batch, n_cols)
             return out if n_cols == self.n_out else out[..., :self.n_out]
-        out = FastfoodStackedFunction.apply(rows, s1, g, s2, n_samples, batch, shared, half, self.fused_backward)
+        out = FastfoodStackedFunction.apply(rows, s1, g, s2, n_samples, batch, shared, half, self.fused_backward,
+                                            self.fused_backward16)
         out = out.view(n_samples, batch, self.D_out)        # (the launch always writes pitch D_out)
         if self.bias is not None:
             out = out + (self.bias.to(x.dtype) if half else self.bias)
