@@ -184,9 +184,10 @@ int whvi_fused_shs_f64(void *dst, const void *src, const void *a, const void *b,
  * sample with WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM -- one transform per sample instead of two, the same
  * multiplies and butterflies in the same order, hence the same bits as the two-transform launch. */
 #define WHVI_FUSED_ONE_TRANSFORM 8
-/* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32 and its backward,
- * whvi_fused_shs_stacked_layer_bwd_f32, only; every other entry refuses them as unknown flags): an nn.ReLU in front of / behind
- * the layer, applied on load / before the store -- max(., 0), NaN passing; in the backward, the masks of those two. */
+/* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32, its 16-bit forms
+ * whvi_fused_shs_stacked_layer_f16 / _bf16 and its backward, whvi_fused_shs_stacked_layer_bwd_f32; every other entry refuses
+ * them as unknown flags): an nn.ReLU in front of / behind the layer, applied on load / before the store -- max(., 0), NaN
+ * passing; in the backward, the masks of those two. */
 #define WHVI_FUSED_RELU_IN      16
 #define WHVI_FUSED_RELU_OUT     32
 
@@ -343,6 +344,32 @@ int whvi_fused_shs_stacked_layer_f32(void *dst, const void *src, const void *a, 
                                      const void *bias /* (n_blocks * D) floats or NULL */,
                                      int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
                                      int64_t n_cols, int64_t ld_dst, int32_t flags, void *stream);
+
+/* whvi_fused_shs_stacked_layer_f32 for 16-bit ACTIVATION storage: dst and src are float16 (_f16) or bfloat16 (_bf16); a, b, c
+ * and the bias stay float32 -- the contract of whvi_fused_shs_stacked_f16 / _bf16: the input is upcast exactly, act_in acts on
+ * the upcast values, every multiply is its own float32 rounding, the butterflies are float32, the bias is added in float32 as a
+ * rounding of its own (skipped without a bias), act_out acts on the float32 sum, and each element is rounded to 16 bits ONCE,
+ * when it is stored: the result is whvi_fused_shs_stacked_layer_f32 on the upcast source, rounded once.  Shapes, row order,
+ * flags (WHVI_FUSED_SRC_SHARED | WHVI_FUSED_RELU_IN | WHVI_FUSED_RELU_OUT) and the meaning of n_cols and ld_dst (in elements) as
+ * there, except that n_cols and ld_dst are multiples of 8 -- a 16-byte chunk holds 8 columns.  With bias == NULL, flags 0 /
+ * WHVI_FUSED_SRC_SHARED and n_cols == ld_dst == n_blocks * D the result is, bit for bit, that of whvi_fused_shs_stacked_f16 /
+ * _bf16.  A row is read once and n_cols columns are written: (D + n_cols) * 2 bytes per row.
+ * Supported: the float32 layer's rule, 6 <= log2d <= 11, n_blocks >= 1 and (12 + 4 * has_bias) * D * n_blocks <= 65536 --
+ * whvi_fused_shs_stacked_layer16_supported(log2d, n_blocks, has_bias) returns 1 exactly then (no device needed).  The same
+ * checks in the same order and with the same codes as whvi_fused_shs_stacked_layer_f32, the overlap check on byte extents of
+ * 2-byte activations (rows * ld_dst of them for dst) and 4-byte vectors, every pointer 16-byte aligned, the bias included, all
+ * before any device call; n_samples * sample_stride == 0 returns WHVI_OK without a launch.  No atomics, no allocation, no
+ * synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_stacked16_layer_kernel<__half | __hip_bfloat16, log2d, K, NT>. */
+int whvi_fused_shs_stacked_layer16_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias);
+int whvi_fused_shs_stacked_layer_f16(void *dst, const void *src, const void *a, const void *b, const void *c,
+                                     const void *bias /* (n_blocks * D) floats or NULL */,
+                                     int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                     int64_t n_cols, int64_t ld_dst, int32_t flags, void *stream);
+int whvi_fused_shs_stacked_layer_bf16(void *dst, const void *src, const void *a, const void *b, const void *c,
+                                      const void *bias /* (n_blocks * D) floats or NULL */,
+                                      int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                      int64_t n_cols, int64_t ld_dst, int32_t flags, void *stream);
 
 /* Backward of whvi_fused_shs_stacked_f32 in ONE launch plus a tiny finishing launch inside the same call.  float32.  Rows as
  * there.  Per row, for j = 0 .. n_blocks - 1, the chain of whvi_fused_shs_bwd_f32 on segment j of grad_y

@@ -6,6 +6,14 @@ warm-up of 30 passes per route (clocks ramp), then the routes ALTERNATE over the
 yardstick is the unfolded route of the same run.
 
     python tools/fastfood_stacked_layer_rate.py --out profiles/r16/fastfood_stacked_layer_rate.json
+    python tools/fastfood_stacked_layer_rate.py --dtype float16 bfloat16 --out profiles/r20/fastfood_stacked_layer16_rate.json
+
+``--dtype float16 | bfloat16`` (default float32; several may be given, one result per shape and dtype): the 16-bit launch
+``_hip.fused_shs_stacked_layer16`` (``WHVIFastfoodStackedMatrix.fused_epilogue16``) against what the layer runs
+with that flag off -- ``_hip.fused_shs_stacked16``, ``+ bias.to(dtype)``, ``torch.relu``, the ``.contiguous()`` -- with 2-byte
+activations throughout, float32 vectors and bias.  There the folded values are NOT the unfolded ones (one rounding instead of
+up to three): ``folded_equals_unfolded`` is recorded as it comes out and ``folded_equals_float32_launch_cast_once`` holds the
+folded launch to ``_hip.fused_shs_stacked_layer(x.float(), ...).to(dtype)``.
 
 Routes:
   ``folded``       ``_hip.fused_shs_stacked_layer`` with a bias and ``relu_out`` (and ``n_cols`` where the shape is narrowed): a row
@@ -35,31 +43,34 @@ SHAPES = ((1024, 4, 16, 8192, False, None), (1024, 4, 16, 8192, True, None), (12
           (2048, 2, 16, 4096, False, None), (256, 4, 16, 8192, False, 800))
 
 
-def one_shape(d, J, S, batch, shared, n_cols, repeats, warmup):
+def one_shape(d, J, S, batch, shared, n_cols, repeats, warmup, dtype=torch.float32):
     dev = torch.device("cuda", 0)
     rows = S * batch
     narrowed = n_cols is not None
     n_cols = J * d if n_cols is None else n_cols
     g = torch.Generator(device=dev).manual_seed(d + J)
-    x = torch.randn(batch if shared else rows, d, device=dev, generator=g)
+    half = dtype != torch.float32
+    size = 2 if half else 4
+    launch, layer = (_hip.fused_shs_stacked16, _hip.fused_shs_stacked_layer16) if half else (_hip.fused_shs_stacked, _hip.fused_shs_stacked_layer)
+    x = torch.randn(batch if shared else rows, d, device=dev, generator=g).to(dtype)
     a = torch.randn(J, d, device=dev, generator=g).mul_(0.01)
     c = torch.randn(J, d, device=dev, generator=g).mul_(0.01)
     b = torch.randn(J, S, d, device=dev, generator=g)
     bias = torch.randn(1, J * d, device=dev, generator=g).mul_(0.1)
-    moved = 4.0 * rows * (d + n_cols)
-    probe_src = torch.empty(2 * rows * d * (1 + J), dtype=torch.uint8, device=dev).random_()
+    moved = float(size) * rows * (d + n_cols)
+    probe_src = torch.empty(size // 2 * rows * d * (1 + J), dtype=torch.uint8, device=dev).random_()
     probe_dst = torch.empty_like(probe_src)
 
     def unfolded(relu):
-        y = _hip.fused_shs_stacked(x, a, b, c, S, batch, shared=shared) + bias
+        y = launch(x, a, b, c, S, batch, shared=shared) + (bias.to(dtype) if half else bias)
         if relu:
             y = torch.relu(y)
         return y[:, :n_cols].contiguous() if narrowed else y
 
     routes = {
-        "folded": lambda: _hip.fused_shs_stacked_layer(x, a, b, c, S, batch, bias=bias, n_cols=n_cols, relu_out=True, shared=shared),
+        "folded": lambda: layer(x, a, b, c, S, batch, bias=bias, n_cols=n_cols, relu_out=True, shared=shared),
         "unfolded": lambda: unfolded(True),
-        "folded_bias": lambda: _hip.fused_shs_stacked_layer(x, a, b, c, S, batch, bias=bias, n_cols=n_cols, shared=shared),
+        "folded_bias": lambda: layer(x, a, b, c, S, batch, bias=bias, n_cols=n_cols, shared=shared),
         "launch_add": lambda: unfolded(False),
         "copy_probe": lambda: _hip.stream_copy_probe(probe_src, probe_dst),
     }
@@ -76,6 +87,11 @@ def one_shape(d, J, S, batch, shared, n_cols, repeats, warmup):
     y = routes["folded"]()
     kernel = _hip.last_kernel()
     same = bool(torch.equal(y + 0.0, routes["unfolded"]() + 0.0)) and bool(torch.equal(routes["folded_bias"](), routes["launch_add"]()))
+    cast_once = None
+    if half:
+        ref = _hip.fused_shs_stacked_layer(x.float(), a, b, c, S, batch, bias=bias, n_cols=n_cols, relu_out=True, shared=shared).to(dtype)
+        cast_once = bool(torch.equal(y + 0.0, ref + 0.0))
+        del ref
     del y
     for name in routes:
         for _ in range(warmup):
@@ -84,9 +100,11 @@ def one_shape(d, J, S, batch, shared, n_cols, repeats, warmup):
     for _ in range(repeats):
         for name in routes:                                         # alternating: one measurement of each route per repeat
             times[name].append(timed(name))
-    out = {"D": d, "n_blocks": J, "n_samples": S, "batch": batch, "rows": rows, "shared_x": shared, "n_cols": n_cols,
+    out = {"dtype": str(dtype).replace("torch.", ""), "D": d, "n_blocks": J, "n_samples": S, "batch": batch, "rows": rows, "shared_x": shared, "n_cols": n_cols,
            "bytes_moved": moved, "copy_probe_bytes": 2.0 * probe_src.numel(), "kernel": kernel, "folded_equals_unfolded": same,
            "routes": {}}
+    if half:
+        out["folded_equals_float32_launch_cast_once"] = cast_once
     for name, ts in times.items():
         med = statistics.median(ts)
         out["routes"][name] = {"ms_median": med, "ms_min": min(ts), "ms_max": max(ts), "ms": ts,
@@ -97,7 +115,7 @@ def one_shape(d, J, S, batch, shared, n_cols, repeats, warmup):
     out["speedup_bias_only"] = r["launch_add"]["ms_median"] / r["folded_bias"]["ms_median"]
     out["folded_bias_max_below_launch_add_min"] = r["folded_bias"]["ms_max"] < r["launch_add"]["ms_min"]
     out["folded_over_copy"] = r["folded"]["ms_median"] / r["copy_probe"]["ms_median"]
-    print(f"D={d:5d} J={J} S={S:3d} B={batch:5d} shared={int(shared)} n_cols={n_cols}: " +
+    print(f"{out['dtype']} D={d:5d} J={J} S={S:3d} B={batch:5d} shared={int(shared)} n_cols={n_cols}: " +
           "; ".join(f"{n} {v['ms_median']:.3f} ms [{v['ms_min']:.3f}-{v['ms_max']:.3f}]" for n, v in r.items()) +
           f"; speedup {out['speedup']:.2f} (bias only {out['speedup_bias_only']:.2f}), folded / copy {out['folded_over_copy']:.2f}, "
           f"slowest folded below fastest unfolded: {out['folded_max_below_unfolded_min']}, same values: {same}", flush=True)
@@ -109,9 +127,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--dtype", nargs="+", default=["float32"], choices=("float32", "float16", "bfloat16"))
     args = ap.parse_args()
     assert args.repeats >= 7, "at least 7 alternating repeats"
-    results = [one_shape(*shape, args.repeats, args.warmup) for shape in SHAPES]
+    results = [one_shape(*shape, args.repeats, args.warmup, getattr(torch, name)) for name in args.dtype for shape in SHAPES]
     doc = {"tool": "tools/fastfood_stacked_layer_rate.py", "argv": sys.argv[1:], "device": torch.cuda.get_device_name(0),
            "repeats": args.repeats, "warmup": args.warmup, "results": results}
     if args.out:

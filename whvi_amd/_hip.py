@@ -140,6 +140,11 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_stacked_layer_supported.argtypes = [i32, i64, i32]
     lib.whvi_fused_shs_stacked_layer_f32.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_layer_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i32, vp]
+    lib.whvi_fused_shs_stacked_layer16_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_layer16_supported.argtypes = [i32, i64, i32]
+    for fn in (lib.whvi_fused_shs_stacked_layer_f16, lib.whvi_fused_shs_stacked_layer_bf16):   # (16-bit: dst and src)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i32, vp]
     lib.whvi_fused_shs_stacked_bwd_supported.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_bwd_supported.argtypes = [i32, i64]
     lib.whvi_fused_shs_stacked_bwd_workspace.restype = i64
@@ -307,7 +312,7 @@ def stream_copy_probe(src: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
 
 
 FUSED_A_PER_SAMPLE, FUSED_C_PER_SAMPLE, FUSED_SRC_SHARED, FUSED_ONE_TRANSFORM = 1, 2, 4, 8
-FUSED_RELU_IN, FUSED_RELU_OUT = 16, 32              # (fused_shs_stacked_layer and fused_shs_stacked_layer_bwd only)
+FUSED_RELU_IN, FUSED_RELU_OUT = 16, 32              # (fused_shs_stacked_layer, fused_shs_stacked_layer16 and fused_shs_stacked_layer_bwd only)
 _HALF_DTYPES = (torch.float16, torch.bfloat16)
 
 
@@ -612,6 +617,67 @@ def fused_shs_stacked_layer(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
                                                     None if bias is None else bias.data_ptr(), J, S, stride, d.bit_length() - 1,
                                                     n_cols, out.stride(0), flags, _stream(src))
     _check(rc, "whvi_fused_shs_stacked_layer")
+    return out
+
+
+def fused_shs_stacked_layer16_supported(dtype: torch.dtype, d: int, n_blocks: int, has_bias: bool) -> bool:
+    """Shapes the one-launch rectangular fastfood layer with its epilogue covers on 16-bit activations
+    (``whvi_fused_shs_stacked_layer16_supported``, restated: no library needed): float16 / bfloat16, and
+    ``fused_shs_stacked_layer_supported``'s rule for the float32 vectors and bias -- 64 <= D <= 2048 and ``n_blocks >= 1`` triples
+    of ``D`` floats, quadruples with a bias, within 64 KiB of LDS."""
+    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return 64 <= d <= 2048 and n_blocks >= 1 and (16 if has_bias else 12) * d * n_blocks <= 65536
+
+
+def fused_shs_stacked_layer16(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int,
+                              sample_stride: int, bias: torch.Tensor = None, n_cols: int = None, relu_in: bool = False,
+                              relu_out: bool = False, shared: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """``fused_shs_stacked_layer`` for float16 / bfloat16 ``src`` with float32 ``a, c`` ``(J, D)``, ``b`` ``(J, n_samples, D)`` and
+    ``bias`` (``J * D`` floats of any shape, or None: no add at all) (whvi_fused_shs_stacked_layer_f16 / _bf16): float32
+    arithmetic on the exactly-upcast input -- ``relu_in``, the three multiplies, the bias add and ``relu_out`` -- and the result
+    in ``src``'s dtype, rounded ONCE when it is stored: ``fused_shs_stacked_layer(src.float(), ...).to(src.dtype)``.  The first
+    ``n_cols`` columns are written (default ``J * D``; a multiple of 8 that ends in the last block).  Returns ``(rows, n_cols)``:
+    a new contiguous tensor, or ``out`` -- a 2-D tensor of ``src``'s dtype with ``stride(1) == 1``, ``stride(0) % 8 == 0``,
+    ``stride(0) >= n_cols`` and a 16-byte aligned base, whose row stride is the launch's pitch; its columns past ``n_cols`` are
+    not written."""
+    S, stride = int(n_samples), int(sample_stride)
+    if src.device.type != "cuda" or src.dim() != 2 or src.dtype not in _HALF_DTYPES:
+        raise RuntimeError("fused_shs_stacked_layer16: src must be a 2-D float16 / bfloat16 CUDA tensor")
+    _require_f32_on_one_device("fused_shs_stacked_layer16 (16-bit activations: a, b, c, bias)", src.device,
+                               (a, b, c) + (() if bias is None else (bias,)))
+    d = src.size(1)
+    if a.dim() != 2 or a.size(1) != d:
+        raise RuntimeError("fused_shs_stacked_layer16: a must be (n_blocks, D)")
+    J = a.size(0)
+    if not fused_shs_stacked_layer16_supported(src.dtype, d, J, bias is not None):
+        raise RuntimeError(f"fused_shs_stacked_layer16: {J} blocks of {d} elements {'with' if bias is not None else 'without'} a "
+                           "bias are outside the supported range (64 <= D <= 2048, (12 + 4 * bias) * D * n_blocks <= 65536)")
+    rows = S * stride
+    n_cols = J * d if n_cols is None else int(n_cols)
+    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d) or \
+            (bias is not None and bias.numel() != J * d):
+        raise RuntimeError("fused_shs_stacked_layer16: operand shapes do not match (src rows must be n_samples * sample_stride, or "
+                           "sample_stride when shared; a, c (J, D); b (J, S, D); bias J * D elements)")
+    if n_cols % 8 != 0 or not (J - 1) * d < n_cols <= J * d:
+        raise RuntimeError(f"fused_shs_stacked_layer16: n_cols = {n_cols} must be a multiple of 8 in ({(J - 1) * d}, {J * d}]")
+    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
+    if bias is not None:
+        bias = _aligned(bias)
+    if out is None:
+        out = torch.empty((rows, n_cols), dtype=src.dtype, device=src.device)
+    elif (out.dim() != 2 or tuple(out.shape) != (rows, n_cols) or out.dtype != src.dtype or out.device != src.device
+          or (rows > 0 and (out.stride(1) != 1 or out.stride(0) % 8 != 0 or out.stride(0) < n_cols)) or out.data_ptr() % 16 != 0):
+        raise RuntimeError("fused_shs_stacked_layer16: bad out tensor")
+    if rows == 0:
+        return out
+    flags = (FUSED_SRC_SHARED if shared else 0) | (FUSED_RELU_IN if relu_in else 0) | (FUSED_RELU_OUT if relu_out else 0)
+    fn = getattr(lib(), "whvi_fused_shs_stacked_layer_" + _DTYPE_SUFFIX[src.dtype])
+    with _OnDevice(src.device):
+        rc = fn(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(),
+                None if bias is None else bias.data_ptr(), J, S, stride, d.bit_length() - 1, n_cols, out.stride(0), flags,
+                _stream(src))
+    _check(rc, "whvi_fused_shs_stacked_layer16")
     return out
 
 

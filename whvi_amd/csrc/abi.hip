@@ -1,6 +1,7 @@
 // whvi_amd/csrc/abi.hip -- dtype-independent part of the C ABI (include/whvi_hip.h).
 #include "dispatch.hpp"
 #include "fused_stacked16.hpp"
+#include "fused_stacked16_layer.hpp"
 
 namespace whvi {
 
@@ -111,11 +112,74 @@ int fused_stacked16_check(FusedStackedArgs &r, bool &launch, void *dst, const vo
     return WHVI_OK;
 }
 
+// ---- the same layer with its epilogue folded in (fused_stacked16_layer.hpp), shared by fused_stacked_layer_f16.hip and
+// fused_stacked_layer_bf16.hip: whvi_fused_shs_stacked_layer_f32's checks in its order, with byte extents of 2-byte activations
+// and 4-byte vectors, and n_cols / ld_dst in whole 8-column chunks
+int fused_stacked16_layer_check(FusedStackedLayerArgs &r, bool &launch, void *dst, const void *src, const void *a, const void *b,
+                                const void *c, const void *bias, int64_t J, int64_t S, int64_t stride, int32_t log2d,
+                                int64_t n_cols, int64_t ld_dst, int32_t flags)
+{
+    g_err[0] = 0;
+    launch = false;
+    if (flags & ~(WHVI_FUSED_SRC_SHARED | WHVI_FUSED_RELU_IN | WHVI_FUSED_RELU_OUT))
+        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: unknown fused flags%s 0x%llx (shared source, ReLU in, ReLU out)", "",
+                    flags);
+    if (J < 0 || S < 0 || stride < 0 || n_cols < 0 || ld_dst < 0)
+        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: negative size%s", "");
+    if (log2d < FUSED_STACKED_MIN_LOG2D || log2d > FUSED_STACKED_MAX_LOG2D)
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: log2(D)%s = %lld is outside the supported range [6, %lld]", "",
+                    log2d, FUSED_STACKED_MAX_LOG2D);
+    const int64_t per_block = (int64_t)(bias ? 16 : 12) << log2d;
+    if (!fused_stacked16_layer_supported(log2d, J, bias != nullptr))
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: %s%lld blocks do not fit 64 KiB of LDS (at most %lld with these operands)",
+                    "", J, FUSED_STACKED_LDS_BYTES / per_block);
+    if ((n_cols | ld_dst) & 7)
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: n_cols%s = %lld and ld_dst = %lld must be multiples of 8", "", n_cols,
+                    ld_dst);
+    if (n_cols <= ((J - 1) << log2d) || n_cols > (J << log2d))
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: n_cols%s = %lld must end in the last of the %lld blocks", "", n_cols,
+                    J);
+    if (ld_dst < n_cols || ld_dst >= ((int64_t)1 << 32))
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: ld_dst%s = %lld is below n_cols = %lld (or beyond 32 bits)", "", ld_dst,
+                    n_cols);
+    if (S == 0 || stride == 0) return WHVI_OK;
+    if (!dst || !src || !a || !b || !c) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: null pointer%s", "");
+    if (S >= ((int64_t)1 << 32) / stride)
+        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: rows are indexed with 32 bits%s", "");
+    if (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)bias) & 15)
+        return fail(WHVI_ERR_ALIGN, "whvi_fused_shs_stacked_layer16: a pointer%s is not 16-byte aligned", "");
+    const FusedBwdGeom geom = fused_bwd_geom(S, stride, log2d);
+    if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: too many blocks%s", "");
+    const int64_t row_bytes = (int64_t)2 << log2d, vec_bytes = (int64_t)4 << log2d, rows = S * stride;
+    const bool shared = (flags & WHVI_FUSED_SRC_SHARED) != 0;
+    const struct { const void *p; int64_t bytes; } ins[] = {
+        {src, (shared ? stride : rows) * row_bytes}, {a, J * vec_bytes}, {b, J * S * vec_bytes}, {c, J * vec_bytes},
+        {bias, bias ? J * vec_bytes : 0}};
+    for (const auto &t : ins)
+        if (t.bytes && ranges_overlap(dst, rows * ld_dst * 2, t.p, t.bytes))
+            return fail(WHVI_ERR_OVERLAP, "whvi_fused_shs_stacked_layer16: dst overlaps an input%s", "");
+    r.dst = dst, r.src = src, r.a = a, r.b = b, r.c = c, r.bias = bias;
+    r.n_blocks = J, r.n_samples = S, r.sample_stride = stride, r.n_cols = n_cols, r.ld_dst = ld_dst, r.log2d = log2d;
+    r.opts = ((flags & WHVI_FUSED_RELU_IN) ? STACKED_OPT_RELU_IN : 0u) | ((flags & WHVI_FUSED_RELU_OUT) ? STACKED_OPT_RELU_OUT : 0u) |
+             (bias ? STACKED_OPT_BIAS : 0u);
+    r.src_shared = shared, r.geom = geom;
+    // the streamed bytes: the n_cols written columns, and the source unless it is shared
+    r.nt = rows * (2 * n_cols + (shared ? 0 : row_bytes)) > NT_MIN_BYTES;
+    launch = true;
+    return WHVI_OK;
+}
+
 }  // namespace whvi
 
 extern "C" __attribute__((visibility("default"))) int whvi_fused_shs_stacked16_supported(int32_t log2d, int64_t n_blocks)
 {
     return fused_stacked16_supported(log2d, n_blocks) ? 1 : 0;
+}
+
+extern "C" __attribute__((visibility("default")))
+int whvi_fused_shs_stacked_layer16_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias)
+{
+    return fused_stacked16_layer_supported(log2d, n_blocks, has_bias != 0) ? 1 : 0;
 }
 
 // per-dtype implementations live in fwht_<dtype>.hip

@@ -34,7 +34,9 @@ of passes of their own over the ``(S, batch, J D)`` activations; a
 ``keep_half = True`` a float16 / bfloat16 input takes ONE launch of ``whvi_fused_shs_stacked_f16 / _bf16`` over the same range
  and the output keeps its dtype; with ``fused_backward = True`` and ``fused_backward16 = True`` as well its backward
 is ONE launch of ``whvi_fused_shs_stacked_bwd_f16 / _bf16`` (``grad_x`` rounded once instead of once per block and
-once per add, which is why it is a flag of its own), per block otherwise; its epilogue stays separate passes.
+once per add, which is why it is a flag of its own), per block otherwise; its epilogue is separate passes unless ``fused_epilogue = True`` and ``fused_epilogue16 = True`` fold it into
+ONE launch of ``whvi_fused_shs_stacked_layer_f16 / _bf16`` (each element rounded once instead of up to three times,
+hence a flag of its own; ``n_out`` a multiple of 8 for the folded narrowing).
 """
 import torch
 import torch.nn as nn
@@ -451,6 +453,52 @@ class FastfoodStackedLayerFunction(torch.autograd.Function):
         return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None
 
 
+class FastfoodStackedLayer16Function(torch.autograd.Function):
+    """``FastfoodStackedLayerFunction`` on 16-bit activations: ``y = act_out(stacked(act_in(x), a, b, c) + bias)[:, :n_cols]`` in
+    ONE launch of ``whvi_fused_shs_stacked_layer_f16 / _bf16`` -- float16 / bfloat16 CUDA ``x``, float32 ``a, b, c``
+    and ``bias`` (``J * D`` elements or None) on its device, a ``(D, J, bias)`` that ``_hip.fused_shs_stacked_layer16_supported``
+    covers, ``n_cols`` a multiple of 8 in ``((J - 1) D, J D]``.  The arithmetic is float32 on the exactly-upcast input and every
+    element is rounded to 16 bits ONCE, where the separate passes (the 16-bit launch, ``+ bias.to(dtype)``, ``torch.relu``) round
+    up to three times: the values are the closer ones, not the same bits.
+
+    Backward: composed from what exists -- the mask of ``relu_out`` from the saved output (saved only then), the bias gradient
+    as the float32 row sum of the masked 16-bit gradient, the gradient zero-padded to ``J * D`` columns, ``act_in(x)``
+    recomputed, ``FastfoodStackedFunction``'s 16-bit backward (``fused_backward`` / ``fused_backward16`` as there), and the mask
+    of ``relu_in`` on ``grad_x``.  First order only."""
+
+    @staticmethod
+    def forward(ctx, x, a, b, c, bias, n_cols, relu_in, relu_out, n_samples, sample_stride, shared=False, fused_backward=False,
+                fused_backward16=False):
+        from whvi_amd import _hip
+        ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
+        ctx.relu_in, ctx.relu_out = bool(relu_in), bool(relu_out)
+        ctx.fused_backward, ctx.fused_backward16 = bool(fused_backward), bool(fused_backward16)
+        y = _hip.fused_shs_stacked_layer16(x, a, b, c, ctx.n_samples, ctx.sample_stride, bias=bias, n_cols=n_cols,
+                                           relu_in=ctx.relu_in, relu_out=ctx.relu_out, shared=ctx.shared)
+        ctx.bias_shape = None if bias is None else bias.shape
+        ctx.save_for_backward(x, a, b, c, y if ctx.relu_out else None)     # (the activation's mask comes from its own output)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_y):
+        x, a, b, c, y = ctx.saved_tensors
+        full = a.numel()                                                   # J * D
+        g = (torch.ops.aten.threshold_backward(grad_y, y, 0) if ctx.relu_out else grad_y).contiguous()
+        grad_bias = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[4]:
+            grad_bias = F.pad(g.sum(dim=0, dtype=torch.float32), (0, full - g.size(1))).view(ctx.bias_shape)
+        if g.size(1) < full:
+            g = F.pad(g, (0, full - g.size(1)))
+        xin = torch.relu(x) if ctx.relu_in else x
+        grad_x, grad_a, grad_b, grad_c = _fastfood_stacked_backward(g, xin, a, b, c, ctx.n_samples, ctx.sample_stride, ctx.shared,
+                                                                    True, ctx.fused_backward, ctx.needs_input_grad[:4],
+                                                                    ctx.fused_backward16)
+        if ctx.relu_in and grad_x is not None:
+            grad_x = torch.ops.aten.threshold_backward(grad_x, xin, 0)
+        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None
+
+
 class WHVIFastfoodStackedMatrix(nn.Module):
     """Rectangular (n_out, n_in) WHVI layer in fastfood mode: ``stack`` square ``WHVIFastfoodMatrix`` blocks of width
     ``D_in = 2^ceil(log2 n_in)`` applied to the zero-padded input, their outputs concatenated and narrowed to ``n_out``
@@ -461,9 +509,10 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     through one forward launch, and with ``fused_backward`` and ``fused_backward16`` as well the backward of all blocks is one
     16-bit launch that rounds ``grad_x`` once."""
     fused_backward = False    # True = the backward of all blocks is one launch (float32, 2 .. 4 blocks of 64 <= D_in <= 1024, 2 of 2048: FastfoodStackedFunction), elsewhere each block's is one launch where FastfoodFunction's is
-    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (forward: one launch for all blocks where _hip.fused_shs_stacked16_supported, per-block launches elsewhere; backward: per block, or one launch with fused_backward16; the epilogue is never folded)
+    keep_half = False         # as on WHVIFastfoodMatrix: 16-bit CUDA activations stay 16-bit (forward: one launch for all blocks where _hip.fused_shs_stacked16_supported, per-block launches elsewhere; backward: per block, or one launch with fused_backward16; the epilogue is separate passes unless fused_epilogue16 folds it)
     fused_backward16 = False  # True (with keep_half and fused_backward) = the 16-bit backward of all blocks is one launch (where _hip.fused_shs_stacked_bwd16_supported: FastfoodStackedFunction); grad_x is rounded once instead of 2 J - 1 times, so its bits differ from the per-block route's; the parameter gradients are bit-equal
     fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
+    fused_epilogue16 = False  # True (with keep_half and fused_epilogue) = on float16 / bfloat16 CUDA activations the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 8) are folded into the 16-bit forward launch (where _hip.fused_shs_stacked_layer16_supported: FastfoodStackedLayer16Function); each element is rounded once instead of up to three times, so its bits differ from the separate passes'
     fused_epilogue_backward = False    # True (with fused_backward and fused_epilogue) = the backward of that launch is one launch too, with both masks and the bias sum folded in (float32, where _hip.fused_shs_stacked_layer_bwd_supported and a ReLU or a narrowing is folded); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
@@ -485,12 +534,20 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     def fuses_relu(self, x):
         """True when ``forward_mc(x, ..., relu_in=, relu_out=)`` folds the activations (and the bias and the narrowing) into its
         one launch: ``fused_epilogue`` set, float32 ``x`` and parameters on one CUDA device (so ``keep_half`` does not apply) and
-        a ``(D_in, stack, bias)`` the launch covers.  Otherwise they are separate ``torch.relu`` passes -- same values either way."""
-        if not self.fused_epilogue or x.device.type != "cuda" or x.dtype != torch.float32:
+        a ``(D_in, stack, bias)`` the launch covers.  Otherwise they are separate ``torch.relu`` passes -- same values either way.
+        With ``fused_epilogue16`` AND ``keep_half`` as well, also for a float16 / bfloat16 ``x`` (float32 parameters on its device,
+        a ``(D_in, stack, bias)`` that ``_hip.fused_shs_stacked_layer16_supported`` covers): the 16-bit launch rounds once where
+        the separate passes round up to three times -- the closer values, not the same bits."""
+        if not self.fused_epilogue or x.device.type != "cuda":
+            return False
+        half = x.dtype in _HALF and self.fused_epilogue16 and self.keep_half
+        if x.dtype != torch.float32 and not half:
             return False
         if any(p.dtype != torch.float32 or p.device != x.device for p in self.parameters()):
             return False
         from whvi_amd import _hip
+        if half:
+            return _hip.fused_shs_stacked_layer16_supported(x.dtype, self.D_in, self.stack, self.bias is not None)
         return _hip.fused_shs_stacked_layer_supported(torch.float32, self.D_in, self.stack, self.bias is not None)
 
     def forward_mc(self, x, n_samples, relu_in=False, relu_out=False):
@@ -513,6 +570,16 @@ class WHVIFastfoodStackedMatrix(nn.Module):
         shared = x.dim() == 2                  # a (batch, D) input shared by all samples: read by every sample, never expanded
         batch = x.size(0) if shared else x.size(1)
         rows = x.contiguous() if shared else x.reshape(n_samples * batch, self.D_in).contiguous()
+        if fold and x.dtype in _HALF:
+            # 16-bit activations (fused_epilogue16): a chunk holds 8 columns, so the narrowing is folded where n_out % 8 == 0
+            narrow = self.n_out < self.D_out and self.n_out % 8 == 0
+            if self.bias is not None or relu_in or relu_out or narrow:
+                n_cols = self.n_out if narrow else self.D_out
+                out = FastfoodStackedLayer16Function.apply(rows, s1, g, s2, self.bias, n_cols, relu_in, relu_out, n_samples, batch,
+                                                           shared, self.fused_backward, self.fused_backward16)
+                out = out.view(n_samples, batch, n_cols)
+                return out if n_cols == self.n_out else out[..., :self.n_out]
+            fold = False                       # nothing to fold: the plain 16-bit launch below
         narrow = self.n_out < self.D_out and self.n_out % 4 == 0
         if fold and (self.bias is not None or relu_in or relu_out or narrow):
             # ONE launch with the epilogue: no pass for the bias, none for a ReLU, and n_out columns written at pitch n_out where
