@@ -767,14 +767,26 @@ int whvi_mlp_fastfood_apply_bwd_f32(void *grad_w_in, void *grad_s1, void *grad_s
  * kernel advances the offset itself when its last block finishes, so nothing about the draw is baked into the
  * launch: safe to capture in a hipGraph (every replay draws fresh eps).  One stream per state at a time.  The
  * stream of numbers is this library's own (not torch.randn's); for bit-level parity work inject eps through
- * whvi_reparam_kl_f32, which computes the same u / sigma / KL from a given eps. */
+ * whvi_reparam_kl_f32, which computes the same u / sigma / KL from a given eps.
+ * The stream is a contract (tools/train_aux_ref.py restates it on the host, tests/test_train_aux_gpu.py holds the kernel to
+ * it): the draw of a launch is a function of (seed, offset, j, k, i) alone.  For element i of matrix j, sample k:
+ *     z = k / 8, q = k % 8, call = q / 4;
+ *     counter = { i,  j << 16 | z,  low32(offset + call),  high32(offset + call) },  key = { low32(seed), high32(seed) };
+ *     x[0..3] = Philox4x32-10(counter, key)   (multipliers D2511F53 / CD9E8D57, key increments 9E3779B9 / BB67AE85);
+ *     the normals q % 4 = 0, 1, 2, 3 are  r(x0) cos t(x1),  r(x0) sin t(x1),  r(x2) cos t(x3),  r(x2) sin t(x3)  with
+ *     u(x) = ((float)(x >> 8) + 0.5f) * 2^-24,  r = sqrtf(-2 logf(u)),  t = 6.283185307179586f * u.
+ * So eight samples take TWO Philox calls of four normals each, and a launch moves the offset on by 2 whatever S is (S = 0
+ * included): after n launches state = {seed, offset + 2 n, 0}.  u(x) maps onto (0, 1] -- the float32 sum rounds once x >> 8
+ * reaches 2^23, and x >> 8 = 2^24 - 1 gives 1.0f, where r = 0 -- never onto 0, so the logarithm is finite. */
 int whvi_reparam_kl_philox_f32(void *u, void *sigma, void *kl_part, void *eps_out, const void *g_mu,
                                const void *g_rho, void *state, int64_t J, int64_t S, int64_t D, float lambda_,
                                void *stream);
 
 /* Backward of whvi_reparam_kl_f32 in one launch (closed form): grad_u (J, 1+S, D) and grad_kl (J) are the incoming
  * gradients (either may be NULL = zero), sigma the forward's saved output; writes grad_mu, grad_rho (J, D).
- * Replaces autograd over softplus / mul / kl_diag_normal (src/weights.py:43-64,82-83; src/utils.py:49-71). */
+ * Replaces autograd over softplus / mul / kl_diag_normal (src/weights.py:43-64,82-83; src/utils.py:49-71).
+ * The formulas assume that 1 / sigma is finite: below g_rho = -88.7 both 1 / sigma and expf(-g_rho) overflow and grad_rho
+ * is inf * 0 = NaN where the exact value is finite (autograd over the op chain gives -inf there). */
 int whvi_reparam_kl_bwd_f32(void *grad_mu, void *grad_rho, const void *grad_u, const void *grad_kl,
                             const void *g_mu, const void *g_rho, const void *eps, const void *sigma,
                             int64_t J, int64_t S, int64_t D, float lambda_, void *stream);

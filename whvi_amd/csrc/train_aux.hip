@@ -59,7 +59,7 @@ __device__ __forceinline__ void normals4(const uint32_t (&x)[4], float (&z)[4])
 {
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-        const float u1 = ((float)(x[2 * p] >> 8) + 0.5f) * 5.9604644775390625e-8f;        // (0, 1), 24 bits
+        const float u1 = ((float)(x[2 * p] >> 8) + 0.5f) * 5.9604644775390625e-8f;        // (0, 1], 24 bits: the + 0.5f rounds from 2^23 on, 1.0f at 2^24 - 1 only
         const float u2 = ((float)(x[2 * p + 1] >> 8) + 0.5f) * 5.9604644775390625e-8f;
         const float rad = sqrtf(-2.0f * logf(u1));
         float sn, cs;
