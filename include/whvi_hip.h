@@ -185,8 +185,8 @@ int whvi_fused_shs_f64(void *dst, const void *src, const void *a, const void *b,
  * multiplies and butterflies in the same order, hence the same bits as the two-transform launch. */
 #define WHVI_FUSED_ONE_TRANSFORM 8
 /* WHVI_FUSED_RELU_IN / WHVI_FUSED_RELU_OUT (whvi_fused_shs_stacked_layer_f32, its 16-bit forms
- * whvi_fused_shs_stacked_layer_f16 / _bf16 and its backward, whvi_fused_shs_stacked_layer_bwd_f32; every other entry refuses
- * them as unknown flags): an nn.ReLU in front of / behind the layer, applied on load / before the store -- max(., 0), NaN
+ * whvi_fused_shs_stacked_layer_f16 / _bf16 and its backward, whvi_fused_shs_stacked_layer_bwd_f32 / _f16 / _bf16; every other
+ * entry refuses them as unknown flags): an nn.ReLU in front of / behind the layer, applied on load / before the store -- max(., 0), NaN
  * passing; in the backward, the masks of those two. */
 #define WHVI_FUSED_RELU_IN      16
 #define WHVI_FUSED_RELU_OUT     32
@@ -469,6 +469,44 @@ int     whvi_fused_shs_stacked_layer_bwd_f32(void *grad_x /* or NULL */, void *g
                                              const void *x, const void *a, const void *b, const void *c,
                                              int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
                                              int64_t n_cols, int64_t ld, int32_t flags, void *stream);
+
+/* Backward of whvi_fused_shs_stacked_layer_f16 / _bf16 in ONE launch plus a tiny finishing launch inside the same call: the call
+ * above on 16-bit activation streams -- its contract on the arithmetic of whvi_fused_shs_stacked_bwd_f16 / _bf16.  grad_y, y, x
+ * and grad_x are __half / __hip_bfloat16; a, b, c, grad_a, grad_b, grad_c, grad_bias and work are float32.  x, grad_y and y are
+ * upcast exactly on load; xin, the select g_j (aten.threshold_backward's semantics, as above), the bias sum and the chain are
+ * float32, nothing is rounded to 16 bits in between; gx stays float32 across the n_blocks segments and
+ *     grad_x = WHVI_FUSED_RELU_IN ? (xin <= 0 ? +0 : round16(gx)) : round16(gx)
+ * is rounded ONCE and stored once per row, or not at all with grad_x == NULL.
+ *   grad_y, y : (n_samples * sample_stride, n_cols) at a common row pitch of ld 2-byte elements; n_cols and ld are multiples of
+ *            8 (a 16-byte chunk); columns n_cols .. ld - 1 and the chunks of the last block past n_cols are never read.
+ *   grad_bias : (n_blocks * D) floats or NULL; all n_blocks * D entries are written, those from n_cols on as +0.
+ *   work   : whvi_fused_shs_stacked_layer_bwd_workspace(...) bytes, unchanged: the grid and the slot of (12 + 4 * has_bias) * D *
+ *            n_blocks bytes are the float32 call's.
+ * grad_x, grad_a, grad_b, grad_c are, bit for bit, whvi_fused_shs_stacked_bwd_f16 / _bf16 on the masked, zero-padded 16-bit g
+ * and on relu(x), followed by the 16-bit mask on grad_x (the select commutes with the one rounding, and the masked 16-bit values
+ * are exact); with no flag, grad_bias == NULL and n_cols == ld == n_blocks * D the call has that entry's bits.  grad_bias is the
+ * float32 sum of the masked gradient in the order described above: deterministic, its own summation order.  No atomics.
+ * (2 * D + (1 + [ReLU out]) * n_cols) * 2 bytes per row.
+ * Supported: 2 <= n_blocks <= 4 for 6 <= log2d <= 10, n_blocks = 2 at log2d = 11, with or without a bias --
+ * whvi_fused_shs_stacked_layer_bwd16_supported(log2d, n_blocks, has_bias) returns 1 exactly then (no device needed).  The checks
+ * of whvi_fused_shs_stacked_layer_bwd_f32 in its order and with its codes, all before any device call, with n_cols and ld
+ * multiples of 8, the extents of grad_y, y (rows * ld), x and grad_x counted in 2-byte elements and those of the vectors in
+ * 4-byte elements; n_samples * sample_stride == 0 returns WHVI_OK without a launch or a write.  No allocation, no
+ * synchronisation: capture-safe.  whvi_last_kernel names
+ * whvi::fused_layer_bwd16_kernel<__half | __hip_bfloat16, log2d, K, n_blocks, has_bias, NT>. */
+int whvi_fused_shs_stacked_layer_bwd16_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias);
+int whvi_fused_shs_stacked_layer_bwd_f16(void *grad_x /* or NULL */, void *grad_a, void *grad_b, void *grad_c,
+                                         void *grad_bias /* (n_blocks * D) floats or NULL */, void *work,
+                                         const void *grad_y, const void *y /* NULL unless WHVI_FUSED_RELU_OUT */,
+                                         const void *x, const void *a, const void *b, const void *c,
+                                         int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                         int64_t n_cols, int64_t ld, int32_t flags, void *stream);
+int whvi_fused_shs_stacked_layer_bwd_bf16(void *grad_x /* or NULL */, void *grad_a, void *grad_b, void *grad_c,
+                                          void *grad_bias /* (n_blocks * D) floats or NULL */, void *work,
+                                          const void *grad_y, const void *y /* NULL unless WHVI_FUSED_RELU_OUT */,
+                                          const void *x, const void *a, const void *b, const void *c,
+                                          int64_t n_blocks, int64_t n_samples, int64_t sample_stride, int32_t log2d,
+                                          int64_t n_cols, int64_t ld, int32_t flags, void *stream);
 
 /* Reparameterisation + KL of J weight matrices in ONE launch, replacing the reference's
  * chain of small ATen kernels: g_sigma = softplus(g_rho) (src/weights.py:43-50), g_sigma * eps per MC sample

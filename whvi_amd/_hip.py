@@ -163,6 +163,11 @@ def _declare_f3(lib):
     lib.whvi_fused_shs_stacked_layer_bwd_f32.restype = ctypes.c_int
     lib.whvi_fused_shs_stacked_layer_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i64,
                                                          i32, vp]
+    lib.whvi_fused_shs_stacked_layer_bwd16_supported.restype = ctypes.c_int
+    lib.whvi_fused_shs_stacked_layer_bwd16_supported.argtypes = [i32, i64, i32]
+    for fn in (lib.whvi_fused_shs_stacked_layer_bwd_f16, lib.whvi_fused_shs_stacked_layer_bwd_bf16):   # (16-bit: grad_x, grad_y, y, x)
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, i32, i64, i64, i32, vp]
     lib.whvi_stream_copy_probe.restype = ctypes.c_int
     lib.whvi_stream_copy_probe.argtypes = [vp, vp, i64, vp]
     lib.whvi_diag_apply_bwd_slabs.restype = ctypes.c_int64
@@ -312,7 +317,7 @@ def stream_copy_probe(src: torch.Tensor, out: torch.Tensor = None) -> torch.Tens
 
 
 FUSED_A_PER_SAMPLE, FUSED_C_PER_SAMPLE, FUSED_SRC_SHARED, FUSED_ONE_TRANSFORM = 1, 2, 4, 8
-FUSED_RELU_IN, FUSED_RELU_OUT = 16, 32              # (fused_shs_stacked_layer, fused_shs_stacked_layer16 and fused_shs_stacked_layer_bwd only)
+FUSED_RELU_IN, FUSED_RELU_OUT = 16, 32              # (fused_shs_stacked_layer, fused_shs_stacked_layer16, fused_shs_stacked_layer_bwd and fused_shs_stacked_layer_bwd16 only)
 _HALF_DTYPES = (torch.float16, torch.bfloat16)
 
 
@@ -893,6 +898,96 @@ def fused_shs_stacked_layer_bwd(grad_y: torch.Tensor, y, x: torch.Tensor, a: tor
                                                     a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride, log2d, n_cols, ld, flags,
                                                     _stream(grad_y))
     _check(rc, "whvi_fused_shs_stacked_layer_bwd")
+    return grad_x, grad_a, grad_b, grad_c, grad_bias
+
+
+def fused_shs_stacked_layer_bwd16_supported(dtype: torch.dtype, d: int, n_blocks: int, has_bias: bool) -> bool:
+    """Shapes the one-launch backward of the rectangular fastfood layer with its epilogue covers on 16-bit activations
+    (``whvi_fused_shs_stacked_layer_bwd16_supported``, restated: no library needed): float16 / bfloat16, and
+    ``fused_shs_stacked_bwd16_supported``'s rule, with or without a bias -- 2 <= ``n_blocks`` <= 4 for 64 <= D <= 1024 and
+    ``n_blocks`` = 2 at D = 2048."""
+    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return (64 <= d <= 1024 and 2 <= n_blocks <= 4) or (d == 2048 and n_blocks == 2)
+
+
+def fused_shs_stacked_layer_bwd16(grad_y: torch.Tensor, y, x: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor,
+                                  n_samples: int, sample_stride: int, n_cols: int = None, relu_in: bool = False,
+                                  relu_out: bool = False, shared: bool = False, need_x: bool = True, need_bias: bool = False,
+                                  grad_x: torch.Tensor = None):
+    """``fused_shs_stacked_layer_bwd`` for float16 / bfloat16 ``grad_y``, ``y`` and ``x`` of one dtype with float32 ``a, c``
+    ``(J, D)`` and ``b`` ``(J, S, D)`` (whvi_fused_shs_stacked_layer_bwd_f16 / _bf16): ``(grad_x | None, grad_a (J, D), grad_b
+    (J, S, D), grad_c (J, D), grad_bias (J * D) | None)``, float32 arithmetic on the exactly-upcast values, the gradients of the
+    vectors and of the bias in float32.  ``grad_y`` may be a view with ``stride(1) == 1``, ``stride(0) % 8 == 0`` and a 16-byte
+    aligned base: its row stride is the launch's pitch and the columns past ``n_cols`` (a multiple of 8) are never read; ``y``
+    must have the same row stride.  ``grad_x`` is in the activations' dtype and is rounded ONCE.  ``grad_x, grad_a, grad_b,
+    grad_c`` have the bits of the separate 16-bit passes (``threshold_backward``, zero padding, ``relu(x)``, the mask on
+    ``grad_x``) around ``fused_shs_stacked_bwd16``; ``grad_bias`` is the float32 column sum of the masked gradient, deterministic
+    with a summation order of its own, zero from ``n_cols`` on.  The workspace comes from torch's allocator, sized by
+    ``whvi_fused_shs_stacked_layer_bwd_workspace``."""
+    S, stride = int(n_samples), int(sample_stride)
+    if grad_y.device.type != "cuda" or grad_y.dim() != 2 or grad_y.dtype not in _HALF_DTYPES:
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: grad_y must be a 2-D float16 / bfloat16 CUDA tensor")
+    act, dev = grad_y.dtype, grad_y.device
+    if not relu_out:
+        y = None
+    elif y is None:
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: relu_out needs the forward's output y")
+    if x.dtype != act or x.device != dev or (y is not None and (y.dtype != act or y.device != dev)):
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: grad_y, y and x must share one 16-bit dtype and device")
+    _require_f32_on_one_device("fused_shs_stacked_layer_bwd16 (16-bit activations: a, b, c)", dev, (a, b, c))
+    if a.dim() != 2 or x.dim() != 2:
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: a must be (n_blocks, D) and x 2-D")
+    J, d = a.shape
+    if not fused_shs_stacked_layer_bwd16_supported(act, d, J, need_bias):
+        raise RuntimeError(f"fused_shs_stacked_layer_bwd16: {J} blocks of {d} elements are outside the supported range "
+                           "(2 .. 4 blocks for 64 <= D <= 1024, 2 blocks at D = 2048)")
+    rows = S * stride
+    n_cols = grad_y.size(1) if n_cols is None else int(n_cols)
+    if n_cols % 8 != 0 or not (J - 1) * d < n_cols <= J * d:
+        raise RuntimeError(f"fused_shs_stacked_layer_bwd16: n_cols = {n_cols} must be a multiple of 8 in ({(J - 1) * d}, {J * d}]")
+    if (tuple(grad_y.shape) != (rows, n_cols) or tuple(x.shape) != ((stride if shared else rows), d) or tuple(c.shape) != (J, d)
+            or tuple(b.shape) != (J, S, d) or (y is not None and tuple(y.shape) != (rows, n_cols))):
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: operand shapes do not match (grad_y and y (n_samples * sample_stride, "
+                           "n_cols); x the same rows of D, or sample_stride rows when shared; a, c (J, D); b (J, S, D))")
+
+    def pitched(t):      # usable as it is (unit column stride, a pitch that is a multiple of 8, an aligned base), or a copy
+        if rows > 1 and t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.stride(0) >= n_cols and t.data_ptr() % 16 == 0:
+            return t
+        return _aligned(t)
+    grad_y = pitched(grad_y)
+    if y is not None:
+        y = pitched(y)
+        if rows > 1 and y.stride(0) != grad_y.stride(0):
+            raise RuntimeError("fused_shs_stacked_layer_bwd16: grad_y and y must have the same row stride")
+    ld = grad_y.stride(0) if rows > 1 else n_cols
+    x, a, b, c = (_aligned(t) for t in (x, a, b, c))
+    if not need_x:
+        grad_x = None
+    elif grad_x is None:
+        grad_x = torch.empty((rows, d), dtype=act, device=dev)
+    elif not grad_x.is_contiguous() or tuple(grad_x.shape) != (rows, d) or grad_x.dtype != act or grad_x.device != dev:
+        raise RuntimeError("fused_shs_stacked_layer_bwd16: bad grad_x tensor")
+    grad_a = torch.empty((J, d), dtype=torch.float32, device=dev)
+    grad_b = torch.empty((J, S, d), dtype=torch.float32, device=dev)
+    grad_c = torch.empty((J, d), dtype=torch.float32, device=dev)
+    grad_bias = torch.empty((J * d,), dtype=torch.float32, device=dev) if need_bias else None
+    if rows == 0:
+        return grad_x, grad_a.zero_(), grad_b.zero_(), grad_c.zero_(), None if grad_bias is None else grad_bias.zero_()
+    L = lib()
+    log2d = d.bit_length() - 1
+    n = int(L.whvi_fused_shs_stacked_layer_bwd_workspace(S, stride, log2d, J, 1 if need_bias else 0))
+    if n < 0:
+        raise RuntimeError(f"whvi_fused_shs_stacked_layer_bwd_workspace failed (code {n})")
+    work = torch.empty((max(n, 16),), dtype=torch.uint8, device=dev)
+    flags = (FUSED_SRC_SHARED if shared else 0) | (FUSED_RELU_IN if relu_in else 0) | (FUSED_RELU_OUT if relu_out else 0)
+    fn = getattr(L, "whvi_fused_shs_stacked_layer_bwd_" + _DTYPE_SUFFIX[act])
+    with _OnDevice(dev):
+        rc = fn(None if grad_x is None else grad_x.data_ptr(), grad_a.data_ptr(), grad_b.data_ptr(), grad_c.data_ptr(),
+                None if grad_bias is None else grad_bias.data_ptr(), work.data_ptr(), grad_y.data_ptr(),
+                None if y is None else y.data_ptr(), x.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride, log2d,
+                n_cols, ld, flags, _stream(grad_y))
+    _check(rc, "whvi_fused_shs_stacked_layer_bwd16")
     return grad_x, grad_a, grad_b, grad_c, grad_bias
 
 

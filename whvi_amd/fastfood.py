@@ -453,6 +453,23 @@ class FastfoodStackedLayerFunction(torch.autograd.Function):
         return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None
 
 
+def _layer_bwd16_pays(d, n_blocks, n_samples, sample_stride, n_cols, relu_out, shared, need_x, need_bias):
+    """Routing of ``FastfoodStackedLayer16Function.backward`` by measurement: False where the one launch measured
+    slower than the composed backward -- four blocks with the bias sum (one wave per SIMD where the composed route's launch runs
+    two) or D = 2048, on a grid of more than 256 blocks (more than one per CU) whose bytes stay in the Infinity Cache (at most
+    256 MiB: the launch's own streaming rule).  Smaller grids and streaming launches measured faster at every such ``(D, J)``."""
+    if not ((n_blocks == 4 and need_bias) or d == 2048):
+        return True
+    rows = n_samples * sample_stride
+    if rows * 2 * (n_cols * (2 if relu_out else 1) + (0 if shared else d) + (d if need_x else 0)) > (256 << 20):
+        return True
+    from whvi_amd import _hip
+    slot = (16 if need_bias else 12) * d * n_blocks          # bytes of one block's slot: the workspace query counts the grid
+    blocks = int(_hip.lib().whvi_fused_shs_stacked_layer_bwd_workspace(n_samples, sample_stride, d.bit_length() - 1, n_blocks,
+                                                                      1 if need_bias else 0)) // slot
+    return blocks <= 256
+
+
 class FastfoodStackedLayer16Function(torch.autograd.Function):
     """``FastfoodStackedLayerFunction`` on 16-bit activations: ``y = act_out(stacked(act_in(x), a, b, c) + bias)[:, :n_cols]`` in
     ONE launch of ``whvi_fused_shs_stacked_layer_f16 / _bf16`` -- float16 / bfloat16 CUDA ``x``, float32 ``a, b, c``
@@ -464,15 +481,29 @@ class FastfoodStackedLayer16Function(torch.autograd.Function):
     Backward: composed from what exists -- the mask of ``relu_out`` from the saved output (saved only then), the bias gradient
     as the float32 row sum of the masked 16-bit gradient, the gradient zero-padded to ``J * D`` columns, ``act_in(x)``
     recomputed, ``FastfoodStackedFunction``'s 16-bit backward (``fused_backward`` / ``fused_backward16`` as there), and the mask
-    of ``relu_in`` on ``grad_x``.  First order only."""
+    of ``relu_in`` on ``grad_x``.  First order only.
+
+    ``fused_epilogue_backward16`` AND ``fused_backward`` AND ``fused_backward16`` (16-bit ``x`` and ``grad_y`` of one dtype on a CUDA
+    device, float32 ``a, b, c`` and ``bias`` on it, rows == n_samples * sample_stride, at least one of ``a, b, c, bias`` wanting a
+    gradient, ``x`` not a shared input that itself wants a gradient, a ``(D, J, bias)`` that
+    ``_hip.fused_shs_stacked_layer_bwd16_supported`` covers, and a mask or a padding to fold -- ``relu_in``, ``relu_out`` or
+    ``n_cols < J * D``; with nothing but the bias sum the case stays composed, as in float32 -- and not one of the cached,
+    full-grid cases that measured slower, ``_layer_bwd16_pays``): the backward is ONE launch of
+    ``whvi_fused_shs_stacked_layer_bwd_f16 / _bf16`` -- both masks, the zero padding and the bias sum inside it, so
+    the masked gradient, its padded copy, ``act_in(x)`` and the unmasked ``grad_x`` are never materialised.  ``grad_x`` and the
+    gradients of ``a, b, c`` have the bits of the composed backward with both backward flags set; the bias gradient is the same
+    float32 sum in another (deterministic) order, which is why this is a flag of its own.  Everything else runs the composed
+    backward."""
 
     @staticmethod
     def forward(ctx, x, a, b, c, bias, n_cols, relu_in, relu_out, n_samples, sample_stride, shared=False, fused_backward=False,
-                fused_backward16=False):
+                fused_backward16=False, fused_epilogue_backward16=False):
         from whvi_amd import _hip
         ctx.n_samples, ctx.sample_stride, ctx.shared = int(n_samples), int(sample_stride), bool(shared)
         ctx.relu_in, ctx.relu_out = bool(relu_in), bool(relu_out)
         ctx.fused_backward, ctx.fused_backward16 = bool(fused_backward), bool(fused_backward16)
+        ctx.fused_epilogue_backward16 = bool(fused_epilogue_backward16)
+        ctx.bias_f32 = bias is None or (bias.dtype == torch.float32 and bias.device == x.device)
         y = _hip.fused_shs_stacked_layer16(x, a, b, c, ctx.n_samples, ctx.sample_stride, bias=bias, n_cols=n_cols,
                                            relu_in=ctx.relu_in, relu_out=ctx.relu_out, shared=ctx.shared)
         ctx.bias_shape = None if bias is None else bias.shape
@@ -484,6 +515,28 @@ class FastfoodStackedLayer16Function(torch.autograd.Function):
     def backward(ctx, grad_y):
         x, a, b, c, y = ctx.saved_tensors
         full = a.numel()                                                   # J * D
+        need_x, need_a, need_b, need_c, need_bias = ctx.needs_input_grad[:5]
+        need_bias = need_bias and ctx.bias_shape is not None
+        S, stride = ctx.n_samples, ctx.sample_stride
+        # a mask or the padding to fold: with the bias sum alone the case stays composed
+        folds = ctx.relu_in or ctx.relu_out or grad_y.size(1) < full
+        if (ctx.fused_epilogue_backward16 and ctx.fused_backward and ctx.fused_backward16 and folds
+                and (need_a or need_b or need_c or need_bias) and not (ctx.shared and need_x) and grad_y.size(0) == S * stride
+                and x.device.type == "cuda" and x.dtype in _HALF and grad_y.dtype == x.dtype and grad_y.device == x.device
+                and ctx.bias_f32 and all(t.dtype == torch.float32 and t.device == x.device for t in (a, b, c))):
+            from whvi_amd import _hip
+            if (_hip.fused_shs_stacked_layer_bwd16_supported(x.dtype, a.size(1), a.size(0), need_bias)
+                    and _layer_bwd16_pays(a.size(1), a.size(0), S, stride, grad_y.size(1), ctx.relu_out, ctx.shared, need_x,
+                                          need_bias)):
+                # ONE launch: the masks, the padding and the bias sum inside it (a shared x that wants a gradient stays
+                # below for _fastfood_stacked_backward's reason)
+                if ctx.relu_out and grad_y.size(0) > 1 and grad_y.stride(0) != y.stride(0):
+                    grad_y = grad_y.contiguous()       # (a view of a wider gradient, e.g. behind torch.cat: y's pitch is n_cols)
+                grad_x, grad_a, grad_b, grad_c, grad_bias = _hip.fused_shs_stacked_layer_bwd16(
+                    grad_y, y, x, a, b, c, S, stride, n_cols=grad_y.size(1), relu_in=ctx.relu_in, relu_out=ctx.relu_out,
+                    shared=ctx.shared, need_x=need_x, need_bias=need_bias)
+                return (grad_x, grad_a if need_a else None, grad_b if need_b else None, grad_c if need_c else None,
+                        grad_bias.view(ctx.bias_shape) if need_bias else None, None, None, None, None, None, None, None, None, None)
         g = (torch.ops.aten.threshold_backward(grad_y, y, 0) if ctx.relu_out else grad_y).contiguous()
         grad_bias = None
         if ctx.bias_shape is not None and ctx.needs_input_grad[4]:
@@ -496,7 +549,7 @@ class FastfoodStackedLayer16Function(torch.autograd.Function):
                                                                     ctx.fused_backward16)
         if ctx.relu_in and grad_x is not None:
             grad_x = torch.ops.aten.threshold_backward(grad_x, xin, 0)
-        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None
+        return grad_x, grad_a, grad_b, grad_c, grad_bias, None, None, None, None, None, None, None, None, None
 
 
 class WHVIFastfoodStackedMatrix(nn.Module):
@@ -514,6 +567,7 @@ class WHVIFastfoodStackedMatrix(nn.Module):
     fused_epilogue = False    # True = the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 4) are folded into the forward launch (float32, where _hip.fused_shs_stacked_layer_supported: FastfoodStackedLayerFunction)
     fused_epilogue16 = False  # True (with keep_half and fused_epilogue) = on float16 / bfloat16 CUDA activations the bias, the neighbouring nn.ReLUs and the narrowing to n_out (a multiple of 8) are folded into the 16-bit forward launch (where _hip.fused_shs_stacked_layer16_supported: FastfoodStackedLayer16Function); each element is rounded once instead of up to three times, so its bits differ from the separate passes'
     fused_epilogue_backward = False    # True (with fused_backward and fused_epilogue) = the backward of that launch is one launch too, with both masks and the bias sum folded in (float32, where _hip.fused_shs_stacked_layer_bwd_supported and a ReLU or a narrowing is folded); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
+    fused_epilogue_backward16 = False  # True (with keep_half, fused_epilogue, fused_epilogue16, fused_backward and fused_backward16) = the backward of the 16-bit epilogue launch is one launch too, with both masks and the bias sum folded in (float16 / bfloat16, where _hip.fused_shs_stacked_layer_bwd16_supported and a ReLU or a narrowing is folded; four blocks with the bias sum, or D_in = 2048, on a full grid of cached bytes stay composed, _layer_bwd16_pays); the bias gradient's bits differ from the composed backward's (another summation order), all other gradients are bit-equal
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
         super().__init__()
@@ -576,7 +630,8 @@ class WHVIFastfoodStackedMatrix(nn.Module):
             if self.bias is not None or relu_in or relu_out or narrow:
                 n_cols = self.n_out if narrow else self.D_out
                 out = FastfoodStackedLayer16Function.apply(rows, s1, g, s2, self.bias, n_cols, relu_in, relu_out, n_samples, batch,
-                                                           shared, self.fused_backward, self.fused_backward16)
+                                                           shared, self.fused_backward, self.fused_backward16,
+                                                           self.fused_epilogue_backward16)
                 out = out.view(n_samples, batch, n_cols)
                 return out if n_cols == self.n_out else out[..., :self.n_out]
             fold = False                       # nothing to fold: the plain 16-bit launch below
