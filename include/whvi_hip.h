@@ -200,6 +200,22 @@ int whvi_fused_shs_ex_f64(void *dst, const void *src, const void *a, const void 
                           int64_t sample_stride, int64_t group_rows, int32_t axis,
                           int32_t flags, void *stream);
 
+/* The launch form whvi_fused_shs_ex_<dtype> (dtype: WHVI_F32, WHVI_F64, WHVI_F16 or WHVI_BF16) takes for these arguments on a
+ * device of `cus` compute units (cus <= 0: the current device's count; cus > 0: no device is touched).  in_place: dst == src;
+ * src_null / c_null: that pointer is NULL.  Returns WHVI_OK and writes, where the pointer is not NULL,
+ *   *stage              which scale vectors a block stages in LDS: 0 none, 1 a and c, 3 a, b and c;
+ *   *nt                 1 for the streaming (non-temporal) instantiation;
+ *   *same_sample_blocks the kernel's block-map word: 0 consecutive tiles per block; 1 the four waves of a block take rows
+ *                       n_samples apart (one sample per block, rows in (batch, sample, D) order); 2 a shared source's order,
+ *                       the sample index fastest within an XCD;
+ *   *grid               the blocks launched (0: nothing is launched).  A streaming launch whose grid is a multiple of 8 walks
+ *                       its blocks in XCD-contiguous order unless same_sample_blocks is 2;
+ * or returns the error code the launch returns for these arguments before it looks at a pointer's value (alignment and overlap
+ * are the launch's to refuse).  Computed by the function the launch itself calls.  Launches nothing. */
+int32_t whvi_fused_shs_plan(int32_t dtype, int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride,
+                            int64_t group_rows, int32_t axis, int32_t flags, int32_t in_place, int32_t src_null, int32_t c_null,
+                            int32_t cus, int32_t *stage, int32_t *nt, int32_t *same_sample_blocks, int64_t *grid);
+
 /* Backward of whvi_fused_shs_f32 with axis = WHVI_AXIS_COL, shared a / c and per-sample b -- y = a (.) H(b_s (.) H(c (.) x)),
  * the fastfood layer -- in ONE launch plus a tiny finishing launch inside the same call.  float32.  Rows are in (sample, row, D)
  * order: n_samples * sample_stride rows, sample s holds rows [s * sample_stride, (s + 1) * sample_stride).  Per row:

@@ -19,7 +19,7 @@ def test_header_declares_the_expected_entry_points():
     syms = _declared_symbols()
     for needed in ("whvi_fwht_f32", "whvi_fwht_f64", "whvi_fwht_f16", "whvi_fwht_bf16", "whvi_fwht_i32",
                    "whvi_fwht_ex", "whvi_fused_shs_f32", "whvi_fused_shs_f64", "whvi_last_error",
-                   "whvi_hip_abi_version", "whvi_max_log2d"):
+                   "whvi_hip_abi_version", "whvi_max_log2d", "whvi_fused_shs_plan"):
         assert needed in syms
 
 
@@ -117,6 +117,17 @@ def test_argument_checks_of_the_fused_flags_without_gpu():
     assert fused(q, None, None, None, None, 4, 9, 2, 2, 1, 1, 8, None) == -1                                         # no source
     assert L.whvi_fused_shs_ex_f64(q, p, None, None, None, 4, 6, 2, 2, 1, 1, 8, None) == -1                          # f64: 512-byte rows
     assert fused(q, p, None, None, None, 0, 9, 2, 2, 1, 1, 12, None) == 0                                            # empty batch
+    # whvi_fused_shs_plan returns the same codes for the same arguments (rows, log2d, n_samples, sample_stride, group_rows, axis,
+    # flags; then in_place, src_null, c_null) and touches no device when the CU count is given
+    plan = lambda *args: _hip.fused_shs_plan(_hip.F32, *args, cus=256)[0]  # noqa: E731
+    assert plan(4, 9, 2, 2, 1, 1, 16, False, False, True) == -1 and "unknown fused flags" in _hip.last_error()
+    assert plan(4, 9, 2, 2, 1, 1, 4, True, False, True) == -5 and "shared source" in _hip.last_error()
+    assert plan(4, 9, 2, 2, 1, 0, 4, False, False, True) == -1 and plan(4, 7, 2, 2, 1, 1, 4, False, False, True) == -1
+    assert plan(4, 9, 2, 2, 1, 1, 8, False, False, False) == -1 and "one-transform" in _hip.last_error()
+    assert plan(4, 9, 2, 2, 1, 1, 8, False, True, True) == -1
+    assert _hip.fused_shs_plan(_hip.F64, 4, 6, 2, 2, 1, 1, 8, False, False, True, cus=256)[0] == -1
+    assert plan(0, 9, 2, 2, 1, 1, 12, False, False, True) == 0 and plan(4, 9, 2, 2, 1, 1, 12, False, False, True) == 0
+    assert _hip.fused_shs_plan(_hip.I32, 4, 9, cus=256)[0] == -1 and "dtype" in _hip.last_error()
 
 
 def test_argument_checks_of_the_training_step_entry_points():

@@ -114,7 +114,9 @@ LARGE = [(5, "from_l2")] + [(k, f) for k in (9, 11, 12, 13) for f in ("one_sampl
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_large_launches_sampled_rows(dtype, log2d, form, mib, hip_lib):
     """320 MiB in place is the streaming instantiation (non-temporal loads, write-through stores, XCD-contiguous block order,
-    store barrier), 96 MiB the cache-resident launch that fills the chip; a row count that is not a multiple of 8 as well."""
+    store barrier), 96 MiB the cache-resident launch that fills the chip; a row count that is not a multiple of 8 as well.
+    (Sampled rows at the timed sizes; tests/test_fused_table_gpu.py compares the whole output of every instantiation, on
+    every block map, at the smallest shape of each regime.)"""
     d, S = 1 << log2d, 64
     nt = mib > 256
     for extra in (0, 3):

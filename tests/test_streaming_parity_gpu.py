@@ -50,7 +50,9 @@ CASES = [(torch.float32, 9), (torch.float32, 10), (torch.float32, 11), (torch.fl
 def test_fused_streaming_instantiation_vs_oracle(dtype, log2d, per_sample, layout, in_place, hip_lib):
     """layout: "batch" = rows in (batch, sample, D) order (sample_stride = 1, BASELINE config 3's order); "sample" =
     (sample, batch, D) with the batch a multiple of the rows per block (fastfood's order: every block inside one sample);
-    "sample_ragged" = the same with an odd batch (blocks straddle samples: no per-block staging of per-sample vectors)."""
+    "sample_ragged" = the same with an odd batch (blocks straddle samples: no per-block staging of per-sample vectors).
+    (Sampled rows at the timed sizes; tests/test_fused_table_gpu.py compares the whole output of every instantiation, on
+    every block map, at the smallest shape of each regime.)"""
     d = 1 << log2d
     esize = 4 if dtype == torch.float32 else 8
     S = 48                                               # not a power of two: the FastDiv row -> sample map

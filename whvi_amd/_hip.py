@@ -174,6 +174,9 @@ def _declare_f3(lib):
     lib.whvi_diag_apply_bwd_slabs.argtypes = [ctypes.c_int32, i64, i64, ctypes.c_int32]
     lib.whvi_diag_apply_order.restype = ctypes.c_int32
     lib.whvi_diag_apply_order.argtypes = [ctypes.c_int32, i64, i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32]
+    p32 = ctypes.POINTER(ctypes.c_int32)
+    lib.whvi_fused_shs_plan.restype = ctypes.c_int32
+    lib.whvi_fused_shs_plan.argtypes = [i32, i64, i32, i64, i64, i64, i32, i32, i32, i32, i32, i32, p32, p32, p32, p64]
 
 
 def lib():
@@ -409,6 +412,19 @@ def fused_shs(src, a=None, b=None, c=None, *, axis: str = "col", n_samples: int 
                 sample_stride, group_rows, ax, flags, _stream(out))
     _check(rc, "whvi_fused_shs")
     return out
+
+
+def fused_shs_plan(dtype_code: int, rows: int, log2d: int, n_samples: int = 1, sample_stride: int = 1, group_rows: int = 1,
+                   axis: int = AXIS_COL, flags: int = 0, in_place: bool = False, src_null: bool = False, c_null: bool = False,
+                   cus: int = 0):
+    """whvi_fused_shs_plan: ``(rc, stage, nt, same_sample_blocks, grid)`` of the launch ``whvi_fused_shs_ex_<dtype>`` makes for
+    these arguments on a device of ``cus`` compute units (0: the current device).  ``dtype_code``: ``F32`` / ``F64`` / ``F16`` /
+    ``BF16``.  Launches nothing; with ``cus > 0`` no device is touched.  ``rc`` is the launch's error code where it refuses."""
+    stage, nt, mode, grid = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int64(-1)
+    rc = int(lib().whvi_fused_shs_plan(int(dtype_code), int(rows), int(log2d), int(n_samples), int(sample_stride), int(group_rows),
+                                       int(axis), int(flags), int(bool(in_place)), int(bool(src_null)), int(bool(c_null)), int(cus),
+                                       ctypes.byref(stage), ctypes.byref(nt), ctypes.byref(mode), ctypes.byref(grid)))
+    return rc, stage.value, nt.value, mode.value, grid.value
 
 
 def fused_shs_bwd_supported(dtype: torch.dtype, d: int) -> bool:

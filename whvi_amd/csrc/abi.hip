@@ -182,6 +182,32 @@ int whvi_fused_shs_stacked_layer16_supported(int32_t log2d, int64_t n_blocks, in
     return fused_stacked16_layer_supported(log2d, n_blocks, has_bias != 0) ? 1 : 0;
 }
 
+// The launch form of whvi_fused_shs_ex_<dtype> for these arguments (include/whvi_hip.h): what fused_plan, the function the
+// launch itself calls, decides.  cus > 0: no device call at all.
+extern "C" __attribute__((visibility("default")))
+int32_t whvi_fused_shs_plan(int32_t dtype, int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride,
+                            int64_t group_rows, int32_t axis, int32_t flags, int32_t in_place, int32_t src_null, int32_t c_null,
+                            int32_t cus, int32_t *stage, int32_t *nt, int32_t *same_sample_blocks, int64_t *grid)
+{
+    FusedPlan p{};
+    int rc;
+    const bool ip = in_place != 0, sn = src_null != 0, cn = c_null != 0;
+    const int n_cu = cus > 0 ? cus : num_cu();
+    switch (dtype) {
+    case WHVI_F32: rc = fused_plan_query<float>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, ip, sn, cn, n_cu, &p); break;
+    case WHVI_F64: rc = fused_plan_query<double>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, ip, sn, cn, n_cu, &p); break;
+    case WHVI_F16: rc = fused_plan_query<__half>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, ip, sn, cn, n_cu, &p); break;
+    case WHVI_BF16: rc = fused_plan_query<__hip_bfloat16>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, ip, sn, cn, n_cu, &p); break;
+    default: g_err[0] = 0; return fail(WHVI_ERR_ARG, "whvi_fused_shs_plan: no fused pipeline for dtype%s %lld", "", dtype);
+    }
+    if (rc != WHVI_OK) return rc;
+    if (stage != nullptr) *stage = p.stage;
+    if (nt != nullptr) *nt = p.nt ? 1 : 0;
+    if (same_sample_blocks != nullptr) *same_sample_blocks = (int32_t)p.same_sample_blocks;
+    if (grid != nullptr) *grid = p.grid;
+    return WHVI_OK;
+}
+
 // per-dtype implementations live in fwht_<dtype>.hip
 extern "C" __attribute__((visibility("hidden"))) int whvi_fwht_variant_f32(void *, const void *, int64_t, int32_t, int32_t, void *);
 extern "C" __attribute__((visibility("hidden"))) int whvi_fwht_variant_f64(void *, const void *, int64_t, int32_t, int32_t, void *);

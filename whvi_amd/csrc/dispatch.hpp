@@ -456,21 +456,90 @@ inline int fwht_dispatch(void *dst, const void *src, int64_t rows, int32_t log2d
 }
 
 // ---- fused pipeline --------------------------------------------------------------------------
+// The launch form of whvi_fused_shs_* as a function of the arguments and the CU count.  ONE place decides it: launch_fused
+// and launch_fused16 launch what fused_plan returns, and whvi_fused_shs_plan (include/whvi_hip.h) reports it, so a test can
+// name the block map a launch took -- whvi_last_kernel cannot: same_sample_blocks and the grid are run-time values.
+struct FusedPlan {
+    int k;                            // 16-byte chunks per lane: pick_k<T, log2d>()
+    int64_t n_chunks, n_tiles, grid;  // grid: blocks of four wave tiles
+    bool big;                         // enough tiles to fill the chip several times over
+    bool nt;                          // the streaming (non-temporal) instantiation
+    int stage;                        // STAGE_* of the instantiation launched
+    uint32_t same_sample_blocks;      // the kernel's run-time block-map word (kernels.hpp): 0, 1 or 2
+};
+
+// pick_k<T, LOG2D>() for a run-time log2(D) (asserted equal wherever launch_fused / launch_fused16 are instantiated)
+template <typename T> constexpr int fused_k(int log2d)
+{
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    const int need = (log2d > LV + 6) ? (1 << (log2d - LV - 6)) : 1;
+    constexpr int stream = 64 / (Elem<T>::VEC * (int)sizeof(typename Elem<T>::acc) / 4);
+    return need > stream ? need : stream;
+}
+
+// rows >= 1 of 2^log2d elements, log2d inside [log2(VEC), max_single_pass_log2d<T>()], arguments the dispatch has accepted
+template <typename T>
+inline FusedPlan fused_plan(int log2d, int64_t rows, int64_t n_samples, int64_t sample_stride, int axis, int flags,
+                            bool src_null, bool in_place, int cus)
+{
+    constexpr int VEC = Elem<T>::VEC;
+    FusedPlan p;
+    p.k = fused_k<T>(log2d);
+    const bool small_tile = p.k * VEC * (int)sizeof(typename Elem<T>::acc) / 4 <= 64;      // tile_vgprs<T, K>() <= 64
+    p.n_chunks = (rows << log2d) / VEC;
+    p.n_tiles = (p.n_chunks + 64 * p.k - 1) / (64 * p.k);
+    p.grid = (p.n_tiles + 3) / 4;
+    // "big": enough tiles to fill the chip several times over (32 per CU; 16 for the 32 KiB tiles of one f64 row of 4096)
+    p.big = p.n_tiles >= (int64_t)(small_tile ? 32 : 16) * cus;
+    // (a shared source is small and cache-resident by intent: the streamed bytes are the destination's)
+    p.nt = p.big && stream_sized(p.n_chunks * 16, in_place || src_null || (flags & WHVI_FUSED_SRC_SHARED) != 0);
+    p.stage = STAGE_NONE;
+    p.same_sample_blocks = 0;
+    const int64_t rows_per_block = ((int64_t)4 * 64 * p.k * VEC) >> log2d;       // >= 1 for every staged shape (log2d <= 12)
+    const bool per_sample_ac = (flags & (WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE)) != 0;
+    if constexpr (sizeof(T) == 2) {
+        // fused_shs16_kernel (launch_fused16 states the rule): D >= 512, launches that fill the chip
+        const bool one_sample_blocks = log2d >= 9 && (n_samples == 1 || sample_stride % rows_per_block == 0);
+        if (log2d >= 9 && p.big) {
+            if (one_sample_blocks && log2d <= 12) p.stage = STAGE_ABC;
+            else if (one_sample_blocks || !per_sample_ac) p.stage = STAGE_AC;
+        }
+        return p;
+    }
+    const bool one_sample_blocks = rows_per_block >= 1 && sample_stride % rows_per_block == 0;
+    if ((flags & WHVI_FUSED_SRC_SHARED) && rows_per_block >= 1 && sample_stride % rows_per_block == 0 &&
+        rows == n_samples * sample_stride && ((sample_stride / rows_per_block) & 7) == 0 && n_samples > 1)
+        p.same_sample_blocks = 2;        // shared source: sample index fastest within an XCD (kernels.hpp)
+    if (p.big) {
+        if (one_sample_blocks || !per_sample_ac) p.stage = STAGE_AC;
+        // per-sample a / c with rows in (batch, sample, D) order and one 128-register row per tile (f64 D = 4096): let every
+        // block take four rows of the same sample, S rows apart, and stage that sample's vectors (kernels.hpp).  Measured
+        // (4 GiB, 64 samples): 3.83 -> 4.63 TB/s.  NOT for 64-register one-row tiles (f32 D = 4096, f64 D = 2048): there
+        // the four rows of a block being 1 MiB apart instead of adjacent costs what the staging gains (5.42 vs 5.55 and
+        // 5.42 vs 5.42 TB/s; the same kernel on contiguous blocks with shared vectors runs at 6.31)
+        else if (!small_tile && rows_per_block == 4 && sample_stride == 1 && n_samples > 1 && axis == WHVI_AXIS_COL &&
+                 !src_null && rows % (4 * n_samples) == 0 && p.n_tiles == rows) {
+            p.stage = STAGE_AC;
+            p.same_sample_blocks = 1;
+        }
+    }
+    // only the tuned column-axis launch (WHVI_FUSED_GEOM: a source, D = 512 .. 4096, big) has staged instantiations
+    if (!(axis == WHVI_AXIS_COL && !src_null && log2d >= 9 && log2d <= 12 && p.big)) p.stage = STAGE_NONE;
+    return p;
+}
+
 template <typename T, int LOG2D, int K = pick_k<T, LOG2D>()>
 inline void launch_fused(void *dst, const void *src, const void *a, const void *b, const void *c,
                          int64_t rows, int64_t n_samples, int64_t sample_stride, int64_t group_rows,
                          int axis, int flags, hipStream_t st)
 {
     constexpr int VEC = Elem<T>::VEC;
-    constexpr bool SMALL_TILE = tile_vgprs<T, K>() <= 64;
-    const int64_t n_chunks = (rows << LOG2D) / VEC;
-    const int64_t n_tiles = (n_chunks + 64 * K - 1) / (64 * K);
+    static_assert(fused_k<T>(LOG2D) == K, "fused_plan's tile is the kernel's");
+    const FusedPlan plan = fused_plan<T>(LOG2D, rows, n_samples, sample_stride, axis, flags, src == nullptr, dst == src, num_cu());
+    const int64_t n_chunks = plan.n_chunks, n_tiles = plan.n_tiles;
     const FastDiv ds = make_fastdiv((uint32_t)sample_stride), dn = make_fastdiv((uint32_t)n_samples),
                   dg = make_fastdiv((uint32_t)group_rows);
-    // "big": enough tiles to fill the chip several times over (32 per CU; 16 for the 32 KiB tiles of one f64 row of 4096)
-    const bool big = n_tiles >= (int64_t)(SMALL_TILE ? 32 : 16) * num_cu();
-    // (a shared source is small and cache-resident by intent: the streamed bytes are the destination's)
-    const bool nt = big && stream_sized(n_chunks * 16, dst, (flags & WHVI_FUSED_SRC_SHARED) ? nullptr : src);
+    const bool big = plan.big, nt = plan.nt;
 #define WHVI_FUSED(AX, EYE, NT, BLK, POL, STG)                                                          \
     do {                                                                                                \
         if constexpr (AX == WHVI_AXIS_COL && !(EYE) && POL == POLICY_DPP && LOG2D - ilog2(VEC) >= 6 && (STG) != STAGE_ABC) { \
@@ -502,7 +571,7 @@ inline void launch_fused(void *dst, const void *src, const void *a, const void *
                            (u32x4 *)dst, (const u32x4 *)src, (const T *)a, (const T *)b, (const T *)c,  \
                            n_chunks, n_tiles, ds, dn, dg, flags, same_sample_blocks);                   \
     } while (0)
-    uint32_t same_sample_blocks = 0;
+    uint32_t same_sample_blocks = plan.same_sample_blocks;
     constexpr bool LDS_OK = sizeof(typename Elem<T>::acc) == 4 && K * VEC == 64;
     constexpr size_t slab_bytes = (size_t)K * (64 * VEC + VEC) * 4;   // lds_slab_floats<VEC, K>() * 4
     (void)LDS_OK;
@@ -533,23 +602,7 @@ inline void launch_fused(void *dst, const void *src, const void *a, const void *
 #else
     constexpr const char *tune_env = nullptr;
 #endif
-    int stage = STAGE_NONE;
-    if ((flags & WHVI_FUSED_SRC_SHARED) && rows_per_block >= 1 && sample_stride % rows_per_block == 0 &&
-        rows == n_samples * sample_stride && ((sample_stride / rows_per_block) & 7) == 0 && n_samples > 1)
-        same_sample_blocks = 2;        // shared source: sample index fastest within an XCD (kernels.hpp)
-    if (big) {
-        if (one_sample_blocks || (flags & (WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE)) == 0) stage = STAGE_AC;
-        // per-sample a / c with rows in (batch, sample, D) order and one 128-register row per tile (f64 D = 4096): let every
-        // block take four rows of the same sample, S rows apart, and stage that sample's vectors (kernels.hpp).  Measured
-        // (4 GiB, 64 samples): 3.83 -> 4.63 TB/s.  NOT for 64-register one-row tiles (f32 D = 4096, f64 D = 2048): there
-        // the four rows of a block being 1 MiB apart instead of adjacent costs what the staging gains (5.42 vs 5.55 and
-        // 5.42 vs 5.42 TB/s; the same kernel on contiguous blocks with shared vectors runs at 6.31)
-        else if (!SMALL_TILE && rows_per_block == 4 && sample_stride == 1 && n_samples > 1 && axis == WHVI_AXIS_COL &&
-                 src != nullptr && rows % (4 * n_samples) == 0 && n_tiles == rows) {
-            stage = STAGE_AC;
-            same_sample_blocks = 1;
-        }
-    }
+    int stage = plan.stage;      // and plan.same_sample_blocks: fused_plan states both rules
     bool use_nt = nt;
     if (tune_env != nullptr) {
         use_nt = tune_env[2] != '0';
@@ -602,6 +655,102 @@ inline void launch_fused(void *dst, const void *src, const void *a, const void *
 #undef WHVI_FUSED
 }
 
+// The checks of whvi_fused_shs_* that need no pointer value -- only which pointers are NULL or equal -- shared by the
+// launch and by whvi_fused_shs_plan, in the launch's order.
+inline int fused_check_sizes(int64_t rows, int64_t n_samples, int64_t sample_stride, int64_t group_rows)
+{
+    if (n_samples < 1 || sample_stride < 1 || group_rows < 1)
+        return fail(WHVI_ERR_ARG, "whvi: n_samples, sample_stride and group_rows must be >= 1%s", "");
+    if (rows >= ((int64_t)1 << 32) || n_samples >= ((int64_t)1 << 32) || sample_stride >= ((int64_t)1 << 32) ||
+        group_rows >= ((int64_t)1 << 32))
+        return fail(WHVI_ERR_SIZE, "whvi: the fused pipeline indexes rows with 32 bits%s", "");
+    return WHVI_OK;
+}
+
+template <typename T>
+inline int fused_check_form(int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride, int64_t group_rows,
+                            int32_t axis, int32_t flags, bool src_null, bool in_place, bool c_null)
+{
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    if (axis != WHVI_AXIS_ROW && axis != WHVI_AXIS_COL)
+        return fail(WHVI_ERR_ARG, "whvi: bad axis%s %lld", "", axis);
+    if (flags & ~(WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE | WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM))
+        return fail(WHVI_ERR_ARG, "whvi: unknown fused flags%s 0x%llx", "", flags);
+    if ((flags & WHVI_FUSED_ONE_TRANSFORM) && (src_null || !c_null || axis != WHVI_AXIS_COL || log2d - LV < 6))
+        return fail(WHVI_ERR_ARG, "whvi: the one-transform flag needs axis = COL, src != NULL, c == NULL and rows of at least "
+                    "64 sixteen-byte chunks%s", "");
+    if ((flags & WHVI_FUSED_SRC_SHARED) && (src_null || in_place || axis != WHVI_AXIS_COL || log2d - LV < 6))
+        return fail(WHVI_ERR_ARG, "whvi: the shared-source flag needs axis = COL, src != NULL, dst != src and rows of at least "
+                    "64 sixteen-byte chunks%s", "");
+    const int rc = fused_check_sizes(rows, n_samples, sample_stride, group_rows);
+    if (rc != WHVI_OK) return rc;
+    if (src_null && (axis != WHVI_AXIS_ROW || group_rows > ((int64_t)1 << log2d)))
+        return fail(WHVI_ERR_ARG, "whvi: src == NULL (identity input) needs axis = ROW and group_rows <= D%s", "");
+    return WHVI_OK;
+}
+
+// The forms that have no 16-bit kernel: the row axis, the identity source, the shared source and the one-transform half.
+template <typename T>
+inline int fused16_check_form(int32_t log2d, int32_t axis, int32_t flags, bool identity_source)
+{
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    if (axis != WHVI_AXIS_ROW && axis != WHVI_AXIS_COL)
+        return fail(WHVI_ERR_ARG, "whvi: bad axis%s %lld", "", axis);
+    if (flags & ~(WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE | WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM))
+        return fail(WHVI_ERR_ARG, "whvi: unknown fused flags%s 0x%llx", "", flags);
+    if (axis == WHVI_AXIS_ROW)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no row-axis form%s: its weight "
+                    "construction is float32", "");
+    if (flags & WHVI_FUSED_SRC_SHARED)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no shared-source form%s: the input is expanded by the caller", "");
+    if (flags & WHVI_FUSED_ONE_TRANSFORM)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no one-transform form%s: a "
+                    "16-bit intermediate would be a second rounding", "");
+    if (identity_source)
+        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no identity-source form (src == NULL)%s", "");
+    if (log2d >= 0 && log2d < LV)
+        return fail(WHVI_ERR_SIZE, "whvi: log2(D)%s = %lld is outside the supported range [3, %lld] of the 16-bit fused pipeline",
+                    "", log2d, max_single_pass_log2d<T>());
+    return WHVI_OK;
+}
+
+// whvi_fused_shs_plan: the plan of the launch whvi_fused_shs_ex_<dtype> makes for these arguments on a device of `cus`
+// compute units, or the error code the launch returns for them before it looks at a pointer's value.  No device call.
+template <typename T>
+inline int fused_plan_query(int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride, int64_t group_rows,
+                            int32_t axis, int32_t flags, bool in_place, bool src_null, bool c_null, int cus, FusedPlan *out)
+{
+    constexpr int LV = ilog2(Elem<T>::VEC);
+    g_err[0] = 0;
+    *out = FusedPlan{};
+    if (in_place && src_null) return fail(WHVI_ERR_ARG, "whvi_fused_shs_plan: in_place with src == NULL%s", "");
+    if constexpr (sizeof(T) == 2) {
+        const int rc = fused16_check_form<T>(log2d, axis, flags, src_null && rows > 0);
+        if (rc != WHVI_OK) return rc;
+    }
+    // (check_common, without the pointers)
+    if (!(rows == 0 && log2d >= 0 && log2d <= max_single_pass_log2d<T>())) {
+        if (rows < 0) return fail(WHVI_ERR_ARG, "whvi: negative row count%s (%lld)", "", rows);
+        if (log2d < 0 || log2d > max_single_pass_log2d<T>())
+            return fail(WHVI_ERR_SIZE, "whvi: log2(D)%s = %lld is outside the supported range [0, %lld]", "", log2d,
+                        max_single_pass_log2d<T>());
+    }
+    // (a shared source in place: the launch's overlap check comes before its check of the flags)
+    if (sizeof(T) != 2 && (flags & WHVI_FUSED_SRC_SHARED) && in_place && rows > 0 && sample_stride >= 1)
+        return fail(WHVI_ERR_OVERLAP, "whvi: dst overlaps the shared source%s", "");
+    int rc;
+    if constexpr (sizeof(T) == 2) rc = fused_check_sizes(rows, n_samples, sample_stride, group_rows);
+    else rc = fused_check_form<T>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, src_null, in_place, c_null);
+    if (rc != WHVI_OK) return rc;
+    if (rows == 0) return WHVI_OK;                    // nothing is launched
+    if (log2d < LV) {                                 // fused_small_kernel: a thread per row, 256 rows per block
+        out->grid = (rows + 255) / 256;
+        return WHVI_OK;
+    }
+    *out = fused_plan<T>(log2d, rows, n_samples, sample_stride, axis, flags, src_null, in_place, cus);
+    return WHVI_OK;
+}
+
 template <typename T>
 inline int fused_dispatch(void *dst, const void *src, const void *a, const void *b, const void *c,
                           int64_t rows, int32_t log2d, int64_t n_samples, int64_t sample_stride,
@@ -619,23 +768,8 @@ inline int fused_dispatch(void *dst, const void *src, const void *a, const void 
         if (sample_stride >= 1 && d < sp + sbytes && sp < d + dbytes)
             return fail(WHVI_ERR_OVERLAP, "whvi: dst overlaps the shared source%s", "");
     }
-    if (axis != WHVI_AXIS_ROW && axis != WHVI_AXIS_COL)
-        return fail(WHVI_ERR_ARG, "whvi: bad axis%s %lld", "", axis);
-    if (flags & ~(WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE | WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM))
-        return fail(WHVI_ERR_ARG, "whvi: unknown fused flags%s 0x%llx", "", flags);
-    if ((flags & WHVI_FUSED_ONE_TRANSFORM) && (src == nullptr || c != nullptr || axis != WHVI_AXIS_COL || log2d - LV < 6))
-        return fail(WHVI_ERR_ARG, "whvi: the one-transform flag needs axis = COL, src != NULL, c == NULL and rows of at least "
-                    "64 sixteen-byte chunks%s", "");
-    if ((flags & WHVI_FUSED_SRC_SHARED) && (src == nullptr || dst == src || axis != WHVI_AXIS_COL || log2d - LV < 6))
-        return fail(WHVI_ERR_ARG, "whvi: the shared-source flag needs axis = COL, src != NULL, dst != src and rows of at least "
-                    "64 sixteen-byte chunks%s", "");
-    if (n_samples < 1 || sample_stride < 1 || group_rows < 1)
-        return fail(WHVI_ERR_ARG, "whvi: n_samples, sample_stride and group_rows must be >= 1%s", "");
-    if (rows >= ((int64_t)1 << 32) || n_samples >= ((int64_t)1 << 32) || sample_stride >= ((int64_t)1 << 32) ||
-        group_rows >= ((int64_t)1 << 32))
-        return fail(WHVI_ERR_SIZE, "whvi: the fused pipeline indexes rows with 32 bits%s", "");
-    if (src == nullptr && (axis != WHVI_AXIS_ROW || group_rows > ((int64_t)1 << log2d)))
-        return fail(WHVI_ERR_ARG, "whvi: src == NULL (identity input) needs axis = ROW and group_rows <= D%s", "");
+    rc = fused_check_form<T>(rows, log2d, n_samples, sample_stride, group_rows, axis, flags, src == nullptr, dst == src, c == nullptr);
+    if (rc != WHVI_OK) return rc;
     if (axis == WHVI_AXIS_COL && (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15)))
         return fail(WHVI_ERR_ALIGN, "whvi: column scale vectors must be 16-byte aligned%s", "");
     if (rows == 0) return WHVI_OK;
@@ -679,13 +813,11 @@ inline void launch_fused16(void *dst, const void *src, const float *a, const flo
                            int64_t n_samples, int64_t sample_stride, int flags, hipStream_t st)
 {
     constexpr int K = pick_k<T, LOG2D>();
-    constexpr int VEC = Elem<T>::VEC;
-    constexpr bool SMALL_TILE = tile_vgprs<T, K>() <= 64;
-    const int64_t n_chunks = (rows << LOG2D) / VEC;
-    const int64_t n_tiles = (n_chunks + 64 * K - 1) / (64 * K);
+    static_assert(fused_k<T>(LOG2D) == K, "fused_plan's tile is the kernel's");
+    const FusedPlan plan = fused_plan<T>(LOG2D, rows, n_samples, sample_stride, WHVI_AXIS_COL, flags, false, dst == src, num_cu());
+    const int64_t n_chunks = plan.n_chunks, n_tiles = plan.n_tiles;
     const FastDiv ds = make_fastdiv((uint32_t)sample_stride), dn = make_fastdiv((uint32_t)n_samples);
-    const bool big = n_tiles >= (int64_t)(SMALL_TILE ? 32 : 16) * num_cu();
-    const bool nt = big && stream_sized(n_chunks * 16, dst, src);
+    const bool nt = plan.nt;
 #define WHVI_FUSED16(NT, STG)                                                                                   \
     do {                                                                                                        \
         constexpr size_t smem = ((STG) == STAGE_ABC ? 3 : ((STG) == STAGE_AC ? 2 : 0)) * sizeof(float) << LOG2D; \
@@ -699,15 +831,13 @@ inline void launch_fused16(void *dst, const void *src, const float *a, const flo
     //     is worth staging, unlike in the f32 kernel: per 16-byte chunk of data a vector is 32 bytes, so three L2-sourced
     //     vectors are six loads per tile load.  D = 8192 stages a and c only (three vectors would be 96 KiB of LDS);
     //   * otherwise shared a / c are staged and per-sample ones come from L2.
+    // (fused_plan applies the rule)
     if constexpr (LOG2D >= 9) {
-        constexpr int64_t rows_per_block = ((int64_t)4 * 64 * K * VEC) >> LOG2D;
-        const bool one_sample_blocks = n_samples == 1 || sample_stride % rows_per_block == 0;
-        const bool shared_ac = (flags & (WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE)) == 0;
-        if (big && one_sample_blocks && LOG2D <= 12) {
+        if (plan.stage == STAGE_ABC) {
             if constexpr (LOG2D <= 12) { if (nt) WHVI_FUSED16(true, STAGE_ABC); else WHVI_FUSED16(false, STAGE_ABC); }
             return;
         }
-        if (big && (one_sample_blocks || shared_ac)) {
+        if (plan.stage == STAGE_AC) {
             if (nt) WHVI_FUSED16(true, STAGE_AC); else WHVI_FUSED16(false, STAGE_AC);
             return;
         }
@@ -731,32 +861,13 @@ inline int fused16_dispatch(void *dst, const void *src, const void *a, const voi
                             int64_t group_rows, int32_t axis, int32_t flags, void *stream)
 {
     static_assert(sizeof(T) == 2, "16-bit storage");
-    constexpr int LV = ilog2(Elem<T>::VEC);
     g_err[0] = 0;
-    if (axis != WHVI_AXIS_ROW && axis != WHVI_AXIS_COL)
-        return fail(WHVI_ERR_ARG, "whvi: bad axis%s %lld", "", axis);
-    if (flags & ~(WHVI_FUSED_A_PER_SAMPLE | WHVI_FUSED_C_PER_SAMPLE | WHVI_FUSED_SRC_SHARED | WHVI_FUSED_ONE_TRANSFORM))
-        return fail(WHVI_ERR_ARG, "whvi: unknown fused flags%s 0x%llx", "", flags);
-    if (axis == WHVI_AXIS_ROW)
-        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no row-axis form%s: its weight "
-                    "construction is float32", "");
-    if (flags & WHVI_FUSED_SRC_SHARED)
-        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no shared-source form%s: the input is expanded by the caller", "");
-    if (flags & WHVI_FUSED_ONE_TRANSFORM)
-        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no one-transform form%s: a "
-                    "16-bit intermediate would be a second rounding", "");
-    if (src == nullptr && dst != nullptr && rows > 0)
-        return fail(WHVI_ERR_ARG, "whvi: the 16-bit fused pipeline has no identity-source form (src == NULL)%s", "");
-    if (log2d >= 0 && log2d < LV)
-        return fail(WHVI_ERR_SIZE, "whvi: log2(D)%s = %lld is outside the supported range [3, %lld] of the 16-bit fused pipeline",
-                    "", log2d, max_single_pass_log2d<T>());
-    int rc = check_common(dst, src, rows, log2d, max_single_pass_log2d<T>(), sizeof(T));
+    int rc = fused16_check_form<T>(log2d, axis, flags, src == nullptr && dst != nullptr && rows > 0);
     if (rc != WHVI_OK) return rc;
-    if (n_samples < 1 || sample_stride < 1 || group_rows < 1)
-        return fail(WHVI_ERR_ARG, "whvi: n_samples, sample_stride and group_rows must be >= 1%s", "");
-    if (rows >= ((int64_t)1 << 32) || n_samples >= ((int64_t)1 << 32) || sample_stride >= ((int64_t)1 << 32) ||
-        group_rows >= ((int64_t)1 << 32))
-        return fail(WHVI_ERR_SIZE, "whvi: the fused pipeline indexes rows with 32 bits%s", "");
+    rc = check_common(dst, src, rows, log2d, max_single_pass_log2d<T>(), sizeof(T));
+    if (rc != WHVI_OK) return rc;
+    rc = fused_check_sizes(rows, n_samples, sample_stride, group_rows);
+    if (rc != WHVI_OK) return rc;
     if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15))
         return fail(WHVI_ERR_ALIGN, "whvi: column scale vectors must be 16-byte aligned%s", "");
     if (rows == 0) return WHVI_OK;
