@@ -664,6 +664,28 @@ int whvi_diag_apply_bwd_f64(void *grad_x, void *out, void *part, const void *g, 
                             const void *s2, const void *u, const void *bias, int64_t S, int64_t B, int32_t log2d,
                             int64_t n_slabs, int32_t flags, void *stream);
 
+/* The batched pass of a reference-mode stacked layer (WHVIStackedMatrix, src/weights.py:111-208) of any width without its
+ * matrices: the stacked weight is J square blocks, each exactly diagonal as written, and ONE launch writes all of them (f32):
+ *     out[s, b, j D + i] = relu?( relu?(x[(s,) b, i]) * w[j, s, i] + 0 (+ bias[j D + i]) )     j < J, i < D, j D + i < n_cols
+ *     w[j, s, i] = wd_j(u[j, 0])_i + wd_j(u[j, 1 + s])_i,     wd_j(v)_i = s1[j, i] * (D * (v_i * s2[j, i]))
+ * with whvi_diag_apply_f32's arithmetic and non-finite rules per block (bit-identical to that launch per block, concatenated and
+ * narrowed to n_cols): a row of x with a non-finite entry at column k, tested after WHVI_DIAG_RELU_IN, has its outputs i != k
+ * NaN in EVERY block and output k of each block the plain product; two such entries make the whole row NaN.
+ *   x      : (S B, D) in (sample, row) order, or (B, D) with WHVI_DIAG_X_SHARED        s1, s2 : (J, D)
+ *   u      : (J, 1 + S, D) with WHVI_DIAG_MEAN_PLUS (whvi_reparam_kl's buffer), else (J, S, D) and w = wd_j(u[j, s]) alone
+ *   bias   : J D floats or NULL
+ *   out    : S B rows at pitch ld_out >= n_cols floats; exactly n_cols columns of each row are written, 1 <= n_cols <= J D,
+ *            columns n_cols .. ld_out - 1 are not touched.  16-byte stores where out is 16-byte aligned and ld_out a multiple
+ *            of 4 (dword stores for a ragged last chunk or another pitch); non-temporal above 256 MiB written.
+ *   flags  : WHVI_DIAG_X_SHARED, _MEAN_PLUS, _RELU_IN, _RELU_OUT; WHVI_DIAG_TUNE_NT / _CACHED force the store form (cross-checks)
+ * Supported (whvi_diag_apply_stacked_supported): log2d in [2, 12], n_blocks >= 1 and one sample's diagonals and bias within
+ * 64 KiB of LDS, 8 J D <= 65536; anything else returns WHVI_ERR_SIZE.  Inputs 16-byte aligned, out 4-byte; out must not
+ * overlap an input (no in-place use); S B < 2^32.  S B == 0 returns WHVI_OK without a launch. */
+int whvi_diag_apply_stacked_supported(int32_t log2d, int64_t n_blocks);
+int whvi_diag_apply_stacked_f32(void *out, const void *x, const void *s1, const void *s2, const void *u, const void *bias,
+                                int64_t S, int64_t B, int32_t log2d, int64_t n_blocks, int64_t n_cols, int64_t ld_out,
+                                int32_t flags, void *stream);
+
 /* The two dense products either side of the square layer in a WHVI regression network, for all Monte-Carlo samples per launch,
  * as HBM-bound streams (f32; same dataflow as the reference's matrix products -- every product is formed, exact zeros of the
  * as-written weights included, so non-finite inputs propagate like in the dense product):

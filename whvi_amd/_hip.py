@@ -100,6 +100,10 @@ def _declare_f3(lib):
         fn = getattr(lib, "whvi_diag_apply_bwd_" + sfx)
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, i64, ctypes.c_int32, vp]
+    lib.whvi_diag_apply_stacked_supported.restype = ctypes.c_int
+    lib.whvi_diag_apply_stacked_supported.argtypes = [ctypes.c_int32, i64]
+    lib.whvi_diag_apply_stacked_f32.restype = ctypes.c_int
+    lib.whvi_diag_apply_stacked_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, i64, i64, i64, ctypes.c_int32, vp]
     lib.whvi_small_k_apply_f32.restype = ctypes.c_int
     lib.whvi_small_k_apply_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_int32, ctypes.c_int32, vp]
     lib.whvi_row_dot_f32.restype = ctypes.c_int
@@ -1257,6 +1261,65 @@ def diag_apply_bwd(grad_out: torch.Tensor, x: torch.Tensor, s1: torch.Tensor, s2
                 n_slabs, flags | int(tune), _stream(x))
     _check(rc, "whvi_diag_apply_bwd")
     return grad_x, out
+
+
+def diag_apply_stacked_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """The rule of ``whvi_diag_apply_stacked_supported`` (include/whvi_hip.h), restated so that it needs no library: float32,
+    D = 4 .. 4096 a power of two, at least one block, and one sample's diagonals and bias -- 8 J D bytes -- within 64 KiB of LDS."""
+    return (dtype == torch.float32 and 4 <= d <= 4096 and (d & (d - 1)) == 0 and n_blocks >= 1 and 8 * n_blocks * d <= 65536)
+
+
+def diag_apply_stacked(x: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, u: torch.Tensor, bias: torch.Tensor = None, *,
+                       n_samples: int, n_cols: int = None, mean_plus: bool = True, relu_in: bool = False, relu_out: bool = False,
+                       out: torch.Tensor = None, tune: int = 0) -> torch.Tensor:
+    """One launch: ``out[k, b, j D + i] = x[(k,) b, i] * (wd_j(u[j, 0]) + wd_j(u[j, 1 + k]))_i + bias[j D + i]`` for the first
+    ``n_cols`` of the J D columns -- the batched pass of a stacked layer without its matrices; see whvi_diag_apply_stacked_f32
+    in include/whvi_hip.h.  ``x``: (S, B, D) or a shared (B, D); ``s1, s2``: (J, D); ``u``: (J, 1 + S, D), or (J, S, D) with
+    ``mean_plus=False``; ``bias``: J D elements or None; returns (S, B, n_cols).  ``out``: a (S, B, n_cols) tensor to write,
+    rows at any pitch >= n_cols (a column slice of a wider buffer: the columns beyond are left alone)."""
+    if x.device.type != "cuda" or x.dtype != torch.float32:
+        raise RuntimeError("diag_apply_stacked: float32 CUDA tensors only")
+    if s1.dim() != 2 or tuple(s2.shape) != tuple(s1.shape):
+        raise RuntimeError("diag_apply_stacked: s1 and s2 must be (n_blocks, D)")
+    J, D = s1.shape
+    if x.shape[-1] != D or not diag_apply_stacked_supported(x.dtype, D, J):
+        raise RuntimeError(f"diag_apply_stacked: D = {x.shape[-1]} with {J} blocks of {D} is outside the supported range")
+    S = int(n_samples)
+    if x.dim() == 3 and x.shape[0] == S:
+        shared, B = False, x.shape[1]
+    elif x.dim() == 2:
+        shared, B = True, x.shape[0]
+    else:
+        raise RuntimeError("diag_apply_stacked: x must be (n_samples, batch, D) or (batch, D)")
+    U = S + (1 if mean_plus else 0)
+    if tuple(u.shape) != (J, U, D):
+        raise RuntimeError(f"diag_apply_stacked: u must be ({J}, {U}, {D})")
+    _require_f32_on_one_device("diag_apply_stacked", x.device, (s1, s2, u) + (() if bias is None else (bias,)))
+    n_cols = J * D if n_cols is None else int(n_cols)
+    if not 1 <= n_cols <= J * D:
+        raise RuntimeError(f"diag_apply_stacked: n_cols = {n_cols} is outside [1, {J * D}]")
+    x, s1, s2, u = _aligned(x), _aligned(s1), _aligned(s2), _aligned(u)
+    if bias is not None:
+        if bias.numel() != J * D:
+            raise RuntimeError("diag_apply_stacked: bias must hold n_blocks * D elements")
+        bias = _aligned(bias.reshape(-1))
+    if out is None:
+        out = torch.empty((S, B, n_cols), dtype=x.dtype, device=x.device)
+        ld = n_cols
+    else:
+        if tuple(out.shape) != (S, B, n_cols) or out.dtype != x.dtype or out.device != x.device:
+            raise RuntimeError("diag_apply_stacked: bad out tensor")
+        ld = out.stride(1) if B > 1 else (out.stride(0) if S > 1 else n_cols)      # the pitch of the S B rows
+        if ld < n_cols or (n_cols > 1 and out.stride(2) != 1) or (B > 1 and S > 1 and out.stride(0) != B * ld):
+            raise RuntimeError("diag_apply_stacked: out must be S B rows at one pitch >= n_cols")
+    flags = ((DIAG_X_SHARED if shared else 0) | (DIAG_MEAN_PLUS if mean_plus else 0) | (DIAG_RELU_IN if relu_in else 0) |
+             (DIAG_RELU_OUT if relu_out else 0))
+    with _OnDevice(x.device):
+        rc = lib().whvi_diag_apply_stacked_f32(out.data_ptr(), x.data_ptr(), s1.data_ptr(), s2.data_ptr(), u.data_ptr(),
+                                               None if bias is None else bias.data_ptr(), S, B, D.bit_length() - 1, J, n_cols,
+                                               int(ld), flags | int(tune), _stream(x))
+    _check(rc, "whvi_diag_apply_stacked")
+    return out
 
 
 APPLY_RELU_IN, APPLY_RELU_OUT = 1, 2

@@ -30,7 +30,7 @@ from whvi_amd.fwht.python import FWHTFunction as fwht_python
 from whvi_amd.fwht.python import WHT_matmul as wht_matmul
 
 __all__ = ["WHVISquarePow2Matrix", "WHVIStackedMatrix", "WHVIColumnMatrix", "WBarFunction", "ReparamKLFunction",
-           "ReparamKLPhiloxFunction", "DiagApplyFunction", "SmallKApplyFunction", "RowDotFunction"]
+           "ReparamKLPhiloxFunction", "DiagApplyFunction", "StackedDiagApplyFunction", "SmallKApplyFunction", "RowDotFunction"]
 
 
 class WBarFunction(torch.autograd.Function):
@@ -198,6 +198,90 @@ class DiagApplyFunction(torch.autograd.Function):
             gx = gx.sum(dim=0)
         grad_bias = tot[2].reshape(ctx.bias_shape) if ctx.bias_shape is not None else None
         return gx, tot[0], tot[1], grad_u, grad_bias, None, None, None, None
+
+
+class StackedDiagApplyFunction(torch.autograd.Function):
+    """``out[k] = (x[(k)] @ W[k].T (+ bias))[..., :n_cols]`` for the stacked weight ``W[k] = cat_j(w_bar_j(u[j, 0]) +
+    w_bar_j(u[j, 1 + k]))`` of every MC sample k in ONE HIP launch that never builds the matrices
+    (``whvi_diag_apply_stacked_f32``, whvi_amd/csrc/diag_apply_stacked.hpp): every block is exactly diagonal as written, so the
+    launch is ``DiagApplyFunction``'s arithmetic per block, written side by side and narrowed to ``n_cols`` columns.
+
+    ``x``: (S, B, D) or a shared (B, D), already zero-padded to D; ``s1, s2``: (J, D); ``u``: (J, 1 + S, D) with
+    ``mean_plus`` else (J, S, D); ``bias``: J D elements or None.  Backward: the closed form as torch ops on the columns that
+    were written -- ``grad_x = sum_j g_j * w_j``, ``grad_w[j, k] = sum_b g_j * x``, the chain to ``s1, s2, u`` of
+    ``DiagApplyFunction.backward``, the masks of both ReLUs and the bias gradient -- no D x D matrix anywhere; under
+    ``create_graph`` the same ops are recorded, so the gradients are differentiable functions of their inputs."""
+
+    @staticmethod
+    def forward(ctx, x, s1, s2, u, bias, n_samples, n_cols, mean_plus, relu_in=False, relu_out=False):
+        from whvi_amd import _hip
+        ctx.n_samples, ctx.n_cols, ctx.mean_plus = int(n_samples), int(n_cols), bool(mean_plus)
+        ctx.relu_in, ctx.relu_out = bool(relu_in), bool(relu_out)
+        ctx.bias_shape = None if bias is None else tuple(bias.shape)
+        out = _hip.diag_apply_stacked(x, s1, s2, u, bias, n_samples=n_samples, n_cols=n_cols, mean_plus=mean_plus,
+                                      relu_in=relu_in, relu_out=relu_out)
+        ctx.save_for_backward(x, s1, s2, u, out if relu_out else None)      # (the activation's mask comes from its own output)
+        return out
+
+    @staticmethod
+    def _reference_ops(x, s1, s2, u, bias, n_cols, mean_plus, relu_in=False, relu_out=False):
+        """The same expression as differentiable torch ops (finite operands)."""
+        J, D = s1.shape
+        w = s1.unsqueeze(1) * (float(D) * (u * s2.unsqueeze(1)))      # (J, U, D): diag(w_bar_j(u[j, r])), the reference's roundings
+        if mean_plus:
+            w = _mean_plus_rest(w, 1)                                 # (J, S, D)
+        if relu_in:
+            x = torch.relu(x)
+        x3 = x if x.dim() == 3 else x.unsqueeze(0)
+        out = (x3.unsqueeze(2) * w.transpose(0, 1).unsqueeze(1)).reshape(w.shape[1], x3.shape[1], J * D)
+        out = out + bias.reshape(-1) if bias is not None else out
+        out = out[..., :n_cols]
+        return torch.relu(out) if relu_out else out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, s1, s2, u, out = ctx.saved_tensors
+        J, D = s1.shape
+        Df, n_cols, mean_plus = float(D), ctx.n_cols, ctx.mean_plus
+        if ctx.relu_out:
+            grad_out = grad_out * (out > 0).to(grad_out.dtype)
+        shared = x.dim() == 2
+        w = s1.unsqueeze(1) * (Df * (u * s2.unsqueeze(1)))            # (J, U, D)
+        w_k = _mean_plus_rest(w, 1) if mean_plus else w               # (J, S, D)
+        S = w_k.shape[1]
+        # the written columns: `full` whole blocks and `rem` columns of the next one (everything beyond has no gradient)
+        full, rem = divmod(n_cols, D)
+        gx = None
+        gw_parts = []
+        for j0, nj, c in ((0, full, D), (full, 1 if rem else 0, rem)):
+            if nj == 0:
+                continue
+            g = grad_out[..., j0 * D:j0 * D + (nj - 1) * D + c].reshape(S, -1, nj, c)      # (S, B, nj, c)
+            xs, ws = x[..., :c], w_k[j0:j0 + nj, :, :c]                                   # ((S,) B, c), (nj, S, c)
+            if ctx.needs_input_grad[0]:
+                part = torch.einsum("sbjc,jsc->bc" if shared else "sbjc,jsc->sbc", g, ws)
+                if ctx.relu_in:
+                    part = part * (xs > 0).to(part.dtype)
+                if c == D:
+                    gx = part
+                elif gx is None:           # a narrow layer (n_cols < D): zeros beyond its columns, nothing else of x's size
+                    gx = part.new_zeros(x.shape)
+                    gx[..., :c] = part
+                else:
+                    gx = gx + F.pad(part, (0, D - c))
+            gw = torch.einsum("sbjc,bc->jsc" if shared else "sbjc,sbc->jsc", g, torch.relu(xs) if ctx.relu_in else xs)   # sum_b g (.) x
+            gw_parts.append(F.pad(gw, (0, D - c)) if c < D else gw)
+        gw = torch.cat(gw_parts, dim=0)
+        if gw.shape[0] < J:
+            gw = F.pad(gw, (0, 0, 0, 0, 0, J - gw.shape[0]))                               # (J, S, D)
+        gw_u = torch.cat((gw.sum(dim=1, keepdim=True), gw), dim=1) if mean_plus else gw     # d w_k / d w_r: (J, U, D)
+        grad_u = gw_u * (s1 * Df * s2).unsqueeze(1)
+        grad_s1 = (gw_u * (Df * (u * s2.unsqueeze(1)))).sum(dim=1)
+        grad_s2 = (gw_u * (s1.unsqueeze(1) * Df * u)).sum(dim=1)
+        grad_bias = None
+        if ctx.bias_shape is not None and ctx.needs_input_grad[4]:
+            grad_bias = F.pad(grad_out.sum(dim=(0, 1)), (0, J * D - n_cols)).reshape(ctx.bias_shape)
+        return gx, grad_s1, grad_s2, grad_u, grad_bias, None, None, None, None, None
 
 
 class SmallKApplyFunction(torch.autograd.Function):
@@ -596,6 +680,9 @@ class _PackedSubMatrix(WHVISquarePow2Matrix):
 class WHVIStackedMatrix(nn.Module):
     inkernel_rng = False      # see WHVISquarePow2Matrix
     hip_apply = True          # batched GPU pass: the narrow-input product as one HIP launch (False: torch.matmul / rocBLAS)
+    # opt-in (WHVINetwork.set_stacked_diagonal): GPU passes apply the blocks' diagonals in ONE launch (StackedDiagApplyFunction:
+    # same values as weight construction + GEMM, no (S, stack * D_in, D_in) weights) wherever the small-K launch does not apply
+    diag_blocks = False
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
         """Arbitrary (n_out, n_in) matrix as a vertical stack of square power-of-two blocks
@@ -735,19 +822,61 @@ class WHVIStackedMatrix(nn.Module):
             return W.reshape(self.stack * self.D_in, self.D_in)
         return torch.cat([weight.sample() for weight in self.weight_matrices])
 
-    def sample_lrt(self, h):
+    def sample_lrt(self, h, _bias=None, _n_cols=None):
+        """``h @ W.T`` with one draw per sub-matrix (src/weights.py:177-180).  ``_bias`` / ``_n_cols`` (``forward``, the
+        ``diag_blocks`` route only): the bias add and the narrowing folded into that route's one launch."""
         if self._on_gpu():
+            if self._diag_blocks_route(h, one_sample=True):
+                # the same draw as below, then one launch on the blocks' diagonals: no (stack * D, D) weight
+                eps = torch.randn(self.stack, self.D_in, device=self._stacked_device())
+                u = torch.stack((self._stacked("g_mu"), F.softplus(self._stacked("g_rho")) * eps), dim=1)      # (stack, 2, D)
+                n_cols = self.stack * self.D_in if _n_cols is None else _n_cols
+                out = self._diag_blocks_apply(h.reshape(1, -1, self.D_in), self._stacked("s1"), self._stacked("s2"), u, _bias,
+                                              1, n_cols)
+                return out.view(*h.shape[:-1], n_cols)
             W = self._stacked_w_bar(lambda mu, sg, eps: [mu, sg * eps], mean_plus=True)   # (stack, 1, D, D)
             W = W.reshape(self.stack * self.D_in, self.D_in)                      # cat over sub-matrices
             return h @ W.T
         return torch.cat([weight.sample_lrt(h) for weight in self.weight_matrices], dim=1)
 
-    def fuses_relu(self, x):
-        """True when the batched pass folds an ``nn.ReLU`` behind this layer into its product's launch (a ReLU in front of it
-        acts on the narrow input and is a negligible op of its own)."""
+    def _small_k_route(self, x):
+        """The batched pass of a narrow shared input as ``whvi_small_k_apply`` (K = D_in = 4 or 8)."""
         from whvi_amd import _hip
         return bool(self.hip_apply and x.dim() == 2 and x.device.type == "cuda" and x.dtype == torch.float32
                     and self.D_in in (4, 8) and _hip.small_k_apply_supported(x.new_empty((1, self.D_in)), self.stack * self.D_in))
+
+    def _diag_blocks_route(self, x, one_sample=False):
+        """True when this pass runs as ONE launch on the blocks' diagonals (``whvi_diag_apply_stacked``): ``diag_blocks`` and
+        ``hip_apply`` set, float32 tensors on one GPU, a supported (D_in, stack), and -- batched passes -- not a shape the
+        small-K launch takes (a shared (batch, n_in) input with D_in = 4 or 8)."""
+        if not (self.diag_blocks and self.hip_apply) or x.dim() < 2 or (not one_sample and x.dim() > 3):
+            return False
+        g_mu = self.packed_g_mu if self._packed else self.weight_matrices[0].g_mu
+        if x.device.type != "cuda" or x.device != g_mu.device or x.dtype != torch.float32 or g_mu.dtype != torch.float32:
+            return False
+        from whvi_amd import _hip
+        if not _hip.diag_apply_stacked_supported(x.dtype, self.D_in, self.stack):
+            return False
+        return one_sample or not self._small_k_route(x)
+
+    def _diag_blocks_apply(self, x, s1, s2, u, bias, n_samples, n_cols, relu_in=False, relu_out=False):
+        """x: (S, B, D_in) or a shared (B, D_in), zero-padded; (S, B, n_cols)."""
+        if not torch.is_grad_enabled():          # inference: the launch itself, without an autograd Function around it
+            from whvi_amd import _hip
+            return _hip.diag_apply_stacked(x, s1, s2, u, bias, n_samples=n_samples, n_cols=n_cols, mean_plus=True,
+                                           relu_in=relu_in, relu_out=relu_out)
+        return StackedDiagApplyFunction.apply(x, s1, s2, u, bias, n_samples, n_cols, True, relu_in, relu_out)
+
+    def fuses_relu(self, x):
+        """True when the batched pass folds an ``nn.ReLU`` behind this layer into its product's launch (a ReLU in front of it
+        acts on the narrow input and is a negligible op of its own) -- and, on the ``diag_blocks`` route, one in front as well."""
+        return self._diag_blocks_route(x) or self._small_k_route(x)
+
+    def _mc_diag_operands(self, n_samples):
+        """(s1 (J, D), s2 (J, D), u (J, 1 + S, D), KL of this pass or None): the draws of ``_mc_operands`` -- the same
+        ``_draw_and_reparam`` call, so the same RNG stream and the same in-kernel Philox option -- without the matrices."""
+        u, kl = _draw_and_reparam(self, self._stacked("g_mu"), self._stacked("g_rho"), n_samples, self.lambda_)
+        return self._stacked("s1"), self._stacked("s2"), u, (None if kl is None else kl.sum())
 
     def _mc_operands(self, n_samples):
         """(W (S, stack * D_in, D_in), KL of this pass or None): every sample's stacked weight of one batched pass (the draws
@@ -769,11 +898,21 @@ class WHVIStackedMatrix(nn.Module):
         """Batched MC forward, see WHVISquarePow2Matrix.forward_mc; ``x``: (batch, n_in) or
         (n_samples, batch, n_in) -> (n_samples, batch, n_out).  Sample k of sub-matrix j uses row
         ``[j, k]`` of one ``randn(stack, n_samples, D_in)`` draw.  ``relu_in`` / ``relu_out``: ``relu(layer(relu(x)))``."""
-        if relu_in:
-            x = torch.relu(x)
+        diag = self._diag_blocks_route(x)
+        if relu_in and not diag:
+            x, relu_in = torch.relu(x), False
         if relu_out and not self.fuses_relu(x):
             return torch.relu(self.forward_mc(x, n_samples))
         D = self.D_in
+        if diag:
+            # one launch on the blocks' diagonals: bias, both activations and the narrowing to n_out folded in
+            s1, s2, u, self._mc_kl = self._mc_diag_operands(n_samples)
+            if self.padding == 0:
+                x_padded = x                                   # n_in == D_in: nothing to pad, no copy of the activations
+            else:
+                x_padded = torch.zeros((*x.size()[:-1], D), device=x.device)
+                x_padded[..., :self.n_in] = x
+            return self._diag_blocks_apply(x_padded, s1, s2, u, self.bias, n_samples, self.n_out, relu_in, relu_out)
         W, self._mc_kl = self._mc_operands(n_samples)                              # (S, stack*D, D)
         x_padded = torch.zeros((*x.size()[:-1], D), device=x.device)
         x_padded[..., :self.n_in] = x
@@ -792,6 +931,8 @@ class WHVIStackedMatrix(nn.Module):
         x_padded = torch.zeros((*x.size()[:-1], self.D_in), device=x.device)
         x_padded[..., :self.n_in] = x
         if use_lrt:
+            if self._on_gpu() and self._diag_blocks_route(x_padded, one_sample=True):
+                return self.sample_lrt(x_padded, self.bias, self.n_out)      # bias and narrowing inside the one launch
             output = self.sample_lrt(x_padded)
             if self.bias is not None:
                 output = output + self.bias
