@@ -686,6 +686,37 @@ int whvi_diag_apply_stacked_f32(void *out, const void *x, const void *s1, const 
                                 int64_t S, int64_t B, int32_t log2d, int64_t n_blocks, int64_t n_cols, int64_t ld_out,
                                 int32_t flags, void *stream);
 
+/* Backward of whvi_diag_apply_stacked_f32 in one call (f32; closed form on the n_cols columns that were written).  With
+ * w[j, s, :] the forward's diagonal (same roundings) and gm = g masked by the output activation:
+ *   grad_x : (S, B, D), grad_x[s, b, i] = [WHVI_DIAG_RELU_IN: x > 0] * sum_{j : j D + i < n_cols} gm[s, b, j D + i] * w[j, s, i]
+ *            -- separate float32 multiplies and adds, in ascending j; +0 where no written column reaches; NULL when the input
+ *            needs no gradient.  With WHVI_DIAG_X_SHARED it is still (S, B, D) and the caller sums it over s.  Non-temporal
+ *            stores above 256 MiB written (WHVI_DIAG_TUNE_NT / _CACHED force the store form).
+ *   out    : (4, J, U, D), U = S (+ 1 with WHVI_DIAG_MEAN_PLUS): whvi_diag_apply_bwd's (4, U, D) layout per block -- slot 0
+ *            dL/du[j, r], slots 1 / 2 sample k's share of dL/ds1[j] / dL/ds2[j] (that call's expressions), slot 3 its share
+ *            of dL/dbias[j D + i] = sum_b gm; with the mean row, row 0 is left to the caller (the sum of rows 1 .. S).  Columns
+ *            j D + i >= n_cols hold zeros in all four slots.
+ *   part   : workspace of S * n_slabs * 2 * C floats, C = 4 * ceil(n_cols / 4) (the written columns: 8 floats per slab for an
+ *            n -> 2 layer, 2 J D at most), n_slabs = whvi_diag_apply_stacked_bwd_slabs(S, B, log2d, J, n_cols): the batch sums
+ *            run over n_slabs row slabs per sample, combined in slab order by a small finishing launch inside the same call
+ *            (deterministic order, no atomics).
+ *   g      : S B rows at pitch ld_g >= n_cols floats, n_cols columns of each read (4-byte aligned; 16-byte loads where g is
+ *            16-byte aligned and ld_g a multiple of 4, dword loads otherwise and for a ragged last chunk)
+ *   x      : the forward's input as it was passed (before a fused WHVI_DIAG_RELU_IN); columns that no written column
+ *            multiplies are not read.          bias : the forward's (J D floats) or NULL, read only with WHVI_DIAG_RELU_OUT
+ * The output activation's mask is recomputed from x, the diagonal and the bias with the forward's roundings, z = relu?(x) * w
+ * + 0 (+ bias): the gradient passes unless relu(z) <= 0 -- on finite data the mask `out > 0` of the saved output; on a NaN
+ * pre-activation it passes (torch's threshold_backward) where a mask taken from the saved output would zero it.  A non-finite
+ * g propagates per element; the forward's row poison is not mimicked.
+ * Supported (whvi_diag_apply_stacked_bwd_supported): log2d in [2, 12], J >= 1, J D <= 8192 (the forward's rule); anything else
+ * returns WHVI_ERR_SIZE.  All pointers 16-byte aligned but g; grad_x, out and part must not overlap an input; S B < 2^32, S <= 65535;
+ * n_slabs must be a slab count of B (ceil(B / ceil(B / n_slabs)) == n_slabs).  S B == 0 returns WHVI_OK without a launch. */
+int whvi_diag_apply_stacked_bwd_supported(int32_t log2d, int64_t n_blocks);
+int64_t whvi_diag_apply_stacked_bwd_slabs(int64_t S, int64_t B, int32_t log2d, int64_t n_blocks, int64_t n_cols);
+int whvi_diag_apply_stacked_bwd_f32(void *grad_x, void *out, void *part, const void *g, const void *x, const void *s1,
+                                    const void *s2, const void *u, const void *bias, int64_t S, int64_t B, int32_t log2d,
+                                    int64_t n_blocks, int64_t n_cols, int64_t ld_g, int64_t n_slabs, int32_t flags, void *stream);
+
 /* The two dense products either side of the square layer in a WHVI regression network, for all Monte-Carlo samples per launch,
  * as HBM-bound streams (f32; same dataflow as the reference's matrix products -- every product is formed, exact zeros of the
  * as-written weights included, so non-finite inputs propagate like in the dense product):

@@ -104,6 +104,13 @@ def _declare_f3(lib):
     lib.whvi_diag_apply_stacked_supported.argtypes = [ctypes.c_int32, i64]
     lib.whvi_diag_apply_stacked_f32.restype = ctypes.c_int
     lib.whvi_diag_apply_stacked_f32.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, i64, i64, i64, ctypes.c_int32, vp]
+    lib.whvi_diag_apply_stacked_bwd_supported.restype = ctypes.c_int
+    lib.whvi_diag_apply_stacked_bwd_supported.argtypes = [ctypes.c_int32, i64]
+    lib.whvi_diag_apply_stacked_bwd_slabs.restype = i64
+    lib.whvi_diag_apply_stacked_bwd_slabs.argtypes = [i64, i64, ctypes.c_int32, i64, i64]
+    lib.whvi_diag_apply_stacked_bwd_f32.restype = ctypes.c_int
+    lib.whvi_diag_apply_stacked_bwd_f32.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, ctypes.c_int32, i64, i64, i64, i64,
+                                                    ctypes.c_int32, vp]
     lib.whvi_small_k_apply_f32.restype = ctypes.c_int
     lib.whvi_small_k_apply_f32.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_int32, ctypes.c_int32, vp]
     lib.whvi_row_dot_f32.restype = ctypes.c_int
@@ -1320,6 +1327,73 @@ def diag_apply_stacked(x: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, u: t
                                                int(ld), flags | int(tune), _stream(x))
     _check(rc, "whvi_diag_apply_stacked")
     return out
+
+
+def diag_apply_stacked_bwd_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
+    """The rule of ``whvi_diag_apply_stacked_bwd_supported`` (include/whvi_hip.h), restated so that it needs no library: float32,
+    D = 4 .. 4096 a power of two, at least one block, and a row of J D <= 8192 columns (eight 16-byte chunks per thread)."""
+    return (dtype == torch.float32 and 4 <= d <= 4096 and (d & (d - 1)) == 0 and n_blocks >= 1 and n_blocks * d <= 8192)
+
+
+def diag_apply_stacked_bwd(grad_out: torch.Tensor, x: torch.Tensor, s1: torch.Tensor, s2: torch.Tensor, u: torch.Tensor, *,
+                           n_samples: int, n_cols: int = None, mean_plus: bool = True, need_grad_x: bool = True,
+                           bias: torch.Tensor = None, relu_in: bool = False, relu_out: bool = False, tune: int = 0):
+    """Backward of ``diag_apply_stacked`` in one call (whvi_diag_apply_stacked_bwd_f32): ``(grad_x (S, B, D) or None, out (4, J,
+    U, D))`` with ``out`` as that call documents it -- per block ``diag_apply_bwd``'s slots (0 dL/du, 1 / 2 the per-sample
+    shares of dL/ds1 / dL/ds2, 3 of dL/dbias; with ``mean_plus`` row 0 is left for the caller's sum over rows 1 ..), zeros from
+    column ``n_cols`` on.  ``grad_out``: (S, B, n_cols), taken at its own pitch when its S B rows have one (a column slice of
+    a wider buffer), made contiguous otherwise.  ``x``: the forward's input; ``bias``: the forward's, read only with
+    ``relu_out`` (its mask is recomputed)."""
+    if x.device.type != "cuda" or x.dtype != torch.float32:
+        raise RuntimeError("diag_apply_stacked_bwd: float32 CUDA tensors only")
+    if s1.dim() != 2 or tuple(s2.shape) != tuple(s1.shape):
+        raise RuntimeError("diag_apply_stacked_bwd: s1 and s2 must be (n_blocks, D)")
+    J, D = s1.shape
+    if x.shape[-1] != D or not diag_apply_stacked_bwd_supported(x.dtype, D, J):
+        raise RuntimeError(f"diag_apply_stacked_bwd: D = {x.shape[-1]} with {J} blocks of {D} is outside the supported range")
+    S = int(n_samples)
+    if x.dim() == 3 and x.shape[0] == S:
+        shared, B = False, x.shape[1]
+    elif x.dim() == 2:
+        shared, B = True, x.shape[0]
+    else:
+        raise RuntimeError("diag_apply_stacked_bwd: x must be (n_samples, batch, D) or (batch, D)")
+    U = S + (1 if mean_plus else 0)
+    if tuple(u.shape) != (J, U, D):
+        raise RuntimeError(f"diag_apply_stacked_bwd: u must be ({J}, {U}, {D})")
+    _require_f32_on_one_device("diag_apply_stacked_bwd", x.device, (grad_out, s1, s2, u) + (() if bias is None else (bias,)))
+    n_cols = J * D if n_cols is None else int(n_cols)
+    if not 1 <= n_cols <= J * D:
+        raise RuntimeError(f"diag_apply_stacked_bwd: n_cols = {n_cols} is outside [1, {J * D}]")
+    if tuple(grad_out.shape) != (S, B, n_cols):
+        raise RuntimeError(f"diag_apply_stacked_bwd: grad_out must be ({S}, {B}, {n_cols})")
+    x, s1, s2, u = _aligned(x), _aligned(s1), _aligned(s2), _aligned(u)
+    if bias is not None:
+        if bias.numel() != J * D:
+            raise RuntimeError("diag_apply_stacked_bwd: bias must hold n_blocks * D elements")
+        bias = _aligned(bias.reshape(-1)) if relu_out else None
+    ld = grad_out.stride(1) if B > 1 else (grad_out.stride(0) if S > 1 else n_cols)      # the pitch of the S B rows
+    if (ld < n_cols or (n_cols > 1 and grad_out.stride(2) != 1) or (B > 1 and S > 1 and grad_out.stride(0) != B * ld)
+            or grad_out.data_ptr() % 4):
+        grad_out, ld = grad_out.contiguous(), n_cols
+    out = torch.empty((4, J, U, D), dtype=x.dtype, device=x.device)
+    grad_x = torch.empty((S, B, D), dtype=x.dtype, device=x.device) if need_grad_x else None
+    if S == 0 or B == 0:
+        out.zero_()
+        return grad_x, out
+    L = lib()
+    log2d = D.bit_length() - 1
+    flags = ((DIAG_X_SHARED if shared else 0) | (DIAG_MEAN_PLUS if mean_plus else 0) | (DIAG_RELU_IN if relu_in else 0) |
+             (DIAG_RELU_OUT if relu_out else 0))
+    with _OnDevice(x.device):
+        n_slabs = int(L.whvi_diag_apply_stacked_bwd_slabs(S, B, log2d, J, n_cols))      # (sized by x's device's CU count)
+        part = torch.empty((S, n_slabs, 2, -(-n_cols // 4) * 4), dtype=x.dtype, device=x.device)      # (the written columns only)
+        rc = L.whvi_diag_apply_stacked_bwd_f32(None if grad_x is None else grad_x.data_ptr(), out.data_ptr(), part.data_ptr(),
+                                               grad_out.data_ptr(), x.data_ptr(), s1.data_ptr(), s2.data_ptr(), u.data_ptr(),
+                                               None if bias is None else bias.data_ptr(), S, B, log2d, J, n_cols, int(ld), n_slabs,
+                                               flags | int(tune), _stream(x))
+    _check(rc, "whvi_diag_apply_stacked_bwd")
+    return grad_x, out
 
 
 APPLY_RELU_IN, APPLY_RELU_OUT = 1, 2

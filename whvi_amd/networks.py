@@ -78,15 +78,18 @@ class WHVINetwork(nn.Module, WHVI):
                 module.hip_apply = not on
         return self
 
-    def set_stacked_diagonal(self, on: bool = True):
+    def set_stacked_diagonal(self, on: bool = True, backward: bool = False):
         """Opt in to the one-launch route of every reference-mode stacked layer (``WHVIStackedMatrix.diag_blocks``): its GPU
         passes apply the diagonals of the stacked blocks directly (``whvi_diag_apply_stacked_f32``: bias, neighbouring ReLUs and
         the narrowing to ``n_out`` in the same launch) instead of building ``(S, stack * D_in, D_in)`` weights and multiplying
         with a batched GEMM -- same draws, same values.  A narrow shared input (D_in = 4 or 8) keeps ``whvi_small_k_apply``;
-        ``set_faithful_dataflow(True)`` switches this route off with the other one-launch routes."""
+        ``set_faithful_dataflow(True)`` switches this route off with the other one-launch routes.  ``backward=True``
+        (``WHVIStackedMatrix.diag_blocks_backward``): that route's backward is one launch too
+        (``whvi_diag_apply_stacked_bwd_f32``) instead of a chain of torch ops with temporaries of activation size."""
         for module in self.modules():
             if hasattr(type(module), "diag_blocks"):
                 module.diag_blocks = bool(on)
+                module.diag_blocks_backward = bool(on) and bool(backward)
         return self
 
     def set_inkernel_rng(self, on: bool = True):

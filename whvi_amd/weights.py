@@ -210,17 +210,30 @@ class StackedDiagApplyFunction(torch.autograd.Function):
     ``mean_plus`` else (J, S, D); ``bias``: J D elements or None.  Backward: the closed form as torch ops on the columns that
     were written -- ``grad_x = sum_j g_j * w_j``, ``grad_w[j, k] = sum_b g_j * x``, the chain to ``s1, s2, u`` of
     ``DiagApplyFunction.backward``, the masks of both ReLUs and the bias gradient -- no D x D matrix anywhere; under
-    ``create_graph`` the same ops are recorded, so the gradients are differentiable functions of their inputs."""
+    ``create_graph`` the same ops are recorded, so the gradients are differentiable functions of their inputs.
+
+    ``native_backward`` (opt-in): the backward is ONE call (``whvi_diag_apply_stacked_bwd_f32``,
+    whvi_amd/csrc/diag_apply_stacked_bwd.hpp: grad_x, the batch sums and the chain to ``s1, s2, u`` and the bias in one launch
+    and a small finishing one) plus one reduction over the samples; ``forward`` then keeps ``x`` and the bias instead of its
+    output, and the output activation's mask is recomputed from them with the forward's roundings -- the saved output's ``out
+    > 0`` on finite data; on a NaN pre-activation the gradient passes (torch's ``threshold_backward``) where the torch ops
+    zero it.  Under ``create_graph``, or for a shape the launch does not cover, the torch ops run with that recomputed mask."""
 
     @staticmethod
-    def forward(ctx, x, s1, s2, u, bias, n_samples, n_cols, mean_plus, relu_in=False, relu_out=False):
+    def forward(ctx, x, s1, s2, u, bias, n_samples, n_cols, mean_plus, relu_in=False, relu_out=False, native_backward=False):
         from whvi_amd import _hip
         ctx.n_samples, ctx.n_cols, ctx.mean_plus = int(n_samples), int(n_cols), bool(mean_plus)
         ctx.relu_in, ctx.relu_out = bool(relu_in), bool(relu_out)
         ctx.bias_shape = None if bias is None else tuple(bias.shape)
         out = _hip.diag_apply_stacked(x, s1, s2, u, bias, n_samples=n_samples, n_cols=n_cols, mean_plus=mean_plus,
                                       relu_in=relu_in, relu_out=relu_out)
-        ctx.save_for_backward(x, s1, s2, u, out if relu_out else None)      # (the activation's mask comes from its own output)
+        if native_backward:
+            # one-launch backward (whvi_diag_apply_stacked_bwd_f32): the activation's mask is recomputed from x, the diagonal and
+            # the bias, so the output is not kept
+            ctx.native_backward = True
+            ctx.save_for_backward(x, s1, s2, u, bias if (bias is not None and relu_out) else None)
+        else:
+            ctx.save_for_backward(x, s1, s2, u, out if relu_out else None)      # (the activation's mask comes from its own output)
         return out
 
     @staticmethod
@@ -239,12 +252,48 @@ class StackedDiagApplyFunction(torch.autograd.Function):
         return torch.relu(out) if relu_out else out
 
     @staticmethod
+    def _native_backward(ctx, grad_out):
+        """``native_backward``: one launch when no graph is recorded and the shape is supported; otherwise the torch ops of
+        ``backward`` with the activation's mask from the recomputed pre-activation (differentiable)."""
+        from whvi_amd import _hip
+        x, s1, s2, u, bias = ctx.saved_tensors
+        J, D = s1.shape
+        if torch.is_grad_enabled() or not _hip.diag_apply_stacked_bwd_supported(x.dtype, D, J) or x.device.type != "cuda":
+            mask = None
+            if ctx.relu_out:
+                with torch.no_grad():      # (a mask: piecewise constant in its operands)
+                    z = StackedDiagApplyFunction._reference_ops(x, s1, s2, u, bias, ctx.n_cols, ctx.mean_plus, ctx.relu_in, False)
+                    mask = (z > 0).to(grad_out.dtype)
+            return StackedDiagApplyFunction._ops_backward(ctx, grad_out, x, s1, s2, u, mask) + (None,)
+        need = ctx.needs_input_grad
+        gx, out = _hip.diag_apply_stacked_bwd(grad_out, x, s1, s2, u, n_samples=ctx.n_samples, n_cols=ctx.n_cols,
+                                              mean_plus=ctx.mean_plus, need_grad_x=need[0], bias=bias, relu_in=ctx.relu_in,
+                                              relu_out=ctx.relu_out)
+        if ctx.mean_plus:
+            # row 0 <- sum of the sample rows: dL/du_mean and the totals of s1 / s2 / bias, one reduction for all four
+            torch.sum(out[:, :, 1:], dim=2, out=out[:, :, 0])
+            grad_u, tot = out[0], out[1:, :, 0]
+        else:
+            grad_u, tot = out[0], (out[1:, :, 0] if ctx.n_samples == 1 else out[1:].sum(dim=2))
+        if gx is not None and x.dim() == 2:
+            gx = gx.sum(dim=0)
+        grad_bias = tot[2].reshape(ctx.bias_shape) if (ctx.bias_shape is not None and need[4]) else None
+        return gx, tot[0], tot[1], grad_u, grad_bias, None, None, None, None, None, None
+
+    @staticmethod
     def backward(ctx, grad_out):
+        if getattr(ctx, "native_backward", False):
+            return StackedDiagApplyFunction._native_backward(ctx, grad_out)
         x, s1, s2, u, out = ctx.saved_tensors
+        mask = (out > 0).to(grad_out.dtype) if ctx.relu_out else None
+        return StackedDiagApplyFunction._ops_backward(ctx, grad_out, x, s1, s2, u, mask) + (None,)
+
+    @staticmethod
+    def _ops_backward(ctx, grad_out, x, s1, s2, u, mask):
         J, D = s1.shape
         Df, n_cols, mean_plus = float(D), ctx.n_cols, ctx.mean_plus
-        if ctx.relu_out:
-            grad_out = grad_out * (out > 0).to(grad_out.dtype)
+        if mask is not None:
+            grad_out = grad_out * mask
         shared = x.dim() == 2
         w = s1.unsqueeze(1) * (Df * (u * s2.unsqueeze(1)))            # (J, U, D)
         w_k = _mean_plus_rest(w, 1) if mean_plus else w               # (J, S, D)
@@ -683,6 +732,9 @@ class WHVIStackedMatrix(nn.Module):
     # opt-in (WHVINetwork.set_stacked_diagonal): GPU passes apply the blocks' diagonals in ONE launch (StackedDiagApplyFunction:
     # same values as weight construction + GEMM, no (S, stack * D_in, D_in) weights) wherever the small-K launch does not apply
     diag_blocks = False
+    # opt-in with it (set_stacked_diagonal(backward=True)): that route's backward as ONE launch as well
+    # (whvi_diag_apply_stacked_bwd_f32) instead of a chain of torch ops
+    diag_blocks_backward = False
 
     def __init__(self, n_in, n_out, lambda_=1e-5, bias=False):
         """Arbitrary (n_out, n_in) matrix as a vertical stack of square power-of-two blocks
@@ -865,7 +917,8 @@ class WHVIStackedMatrix(nn.Module):
             from whvi_amd import _hip
             return _hip.diag_apply_stacked(x, s1, s2, u, bias, n_samples=n_samples, n_cols=n_cols, mean_plus=True,
                                            relu_in=relu_in, relu_out=relu_out)
-        return StackedDiagApplyFunction.apply(x, s1, s2, u, bias, n_samples, n_cols, True, relu_in, relu_out)
+        return StackedDiagApplyFunction.apply(x, s1, s2, u, bias, n_samples, n_cols, True, relu_in, relu_out,
+                                              bool(self.diag_blocks_backward))
 
     def fuses_relu(self, x):
         """True when the batched pass folds an ``nn.ReLU`` behind this layer into its product's launch (a ReLU in front of it
