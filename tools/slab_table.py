@@ -30,8 +30,8 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from kernel_table import NT_MIN_BYTES, family  # noqa: E402,F401
 
 MIN_LOG2D, MAX_LOG2D = 6, 12                   # fused_bwd.hpp: FUSED_BWD_MIN_LOG2D / FUSED_BWD_MAX_LOG2D
-STACKED_MAX_LOG2D = 11                         # fused_stacked.hpp: FUSED_STACKED_MAX_LOG2D
-LDS_BYTES = 65536                              # fused_stacked.hpp: FUSED_STACKED_LDS_BYTES
+STACKED_MAX_LOG2D = 11                         # fused_stacked_fwd.hpp: FUSED_STACKED_MAX_LOG2D
+LDS_BYTES = 65536                              # fused_stacked_fwd.hpp: FUSED_STACKED_LDS_BYTES
 SAMPLES = 3                                    # every case: an odd sample count, so the slab count does not divide evenly
 
 KERNEL_FAMILIES = ("fused_shs_bwd_kernel", "fused_shs_stacked_kernel", "fused_stacked16_kernel", "fused_shs_stacked_bwd_kernel",

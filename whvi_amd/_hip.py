@@ -506,12 +506,84 @@ def fused_shs_bwd(grad_y: torch.Tensor, x: torch.Tensor, a: torch.Tensor, b: tor
     return grad_x, grad_a, grad_b, grad_c
 
 
+_F32_DTYPES = (torch.float32,)
+
+
+def _stacked_fwd_rule(dtype, dtypes, d: int, n_blocks: int, has_bias: bool) -> bool:
+    """The one support rule of the stacked forward launches (fused_stacked_layer_supported, fused_stacked_fwd.hpp, restated):
+    the staged vectors and the bias are float32 whatever the activations are stored in."""
+    if dtype not in dtypes or d < 1 or (d & (d - 1)) != 0:
+        return False
+    return 64 <= d <= 2048 and n_blocks >= 1 and (16 if has_bias else 12) * d * n_blocks <= 65536
+
+
+def _fused_shs_stacked_fwd(name: str, dtypes, layer: bool, src, a, b, c, n_samples, sample_stride, shared, out,
+                           bias=None, n_cols=None, relu_in=False, relu_out=False):
+    """The one implementation behind ``fused_shs_stacked{,16}`` and ``fused_shs_stacked_layer{,16}``.  ``name``: the binding (the
+    prefix of its messages; ``whvi_`` + ``name`` names the entry's errors); ``dtypes``: the activation dtypes it takes -- float32,
+    or the 16-bit ones, whose chunk of 16 bytes is 8 columns and whose ``a, b, c, bias`` stay float32; ``layer``: the entry with
+    the epilogue (``bias``, ``n_cols``, the two ReLUs and a pitched ``out``)."""
+    half = dtypes is _HALF_DTYPES
+    mult = 8 if half else 4                       # columns of a 16-byte chunk
+    S, stride = int(n_samples), int(sample_stride)
+    biases = () if bias is None else (bias,)
+    if half:
+        if src.device.type != "cuda" or src.dim() != 2 or src.dtype not in dtypes:
+            raise RuntimeError(f"{name}: src must be a 2-D float16 / bfloat16 CUDA tensor")
+        _require_f32_on_one_device(f"{name} (16-bit activations: a, b, c{', bias' if layer else ''})", src.device, (a, b, c) + biases)
+    else:
+        if src.device.type != "cuda" or src.dim() != 2:
+            raise RuntimeError(f"{name}: src must be a 2-D CUDA tensor")
+        _require_f32_on_one_device(name, src.device, (src, a, b, c) + biases)
+    d = src.size(1)
+    if a.dim() != 2 or a.size(1) != d:
+        raise RuntimeError(f"{name}: a must be (n_blocks, D)")
+    J = a.size(0)
+    if not _stacked_fwd_rule(src.dtype, dtypes, d, J, bias is not None):
+        if layer:
+            raise RuntimeError(f"{name}: {J} blocks of {d} elements {'with' if bias is not None else 'without'} a bias "
+                               "are outside the supported range (64 <= D <= 2048, (12 + 4 * bias) * D * n_blocks <= 65536)")
+        raise RuntimeError(f"{name}: {J} blocks of {d} elements are outside the supported range "
+                           "(64 <= D <= 2048, 12 * D * n_blocks <= 65536)")
+    rows = S * stride
+    n_cols = J * d if n_cols is None else int(n_cols)
+    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d) or \
+            (bias is not None and bias.numel() != J * d):
+        raise RuntimeError(f"{name}: operand shapes do not match (src rows must be n_samples * sample_stride, or "
+                           f"sample_stride when shared; a, c (J, D); b (J, S, D){'; bias J * D elements' if layer else ''})")
+    if n_cols % mult != 0 or not (J - 1) * d < n_cols <= J * d:
+        raise RuntimeError(f"{name}: n_cols = {n_cols} must be a multiple of {mult} in ({(J - 1) * d}, {J * d}]")
+    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
+    if bias is not None:
+        bias = _aligned(bias)
+    if out is None:
+        out = torch.empty((rows, n_cols), dtype=src.dtype, device=src.device)
+    else:
+        ok = out.dim() == 2 and tuple(out.shape) == (rows, n_cols) and out.dtype == src.dtype and out.device == src.device
+        if layer:                                 # its row stride is the launch's pitch
+            ok = ok and (rows == 0 or (out.stride(1) == 1 and out.stride(0) % mult == 0 and out.stride(0) >= n_cols)) \
+                and out.data_ptr() % 16 == 0
+        else:
+            ok = ok and out.is_contiguous()
+        if not ok:
+            raise RuntimeError(f"{name}: bad out tensor")
+    if rows == 0:
+        return out
+    flags = (FUSED_SRC_SHARED if shared else 0) | (FUSED_RELU_IN if relu_in else 0) | (FUSED_RELU_OUT if relu_out else 0)
+    fn = getattr(lib(), f"whvi_fused_shs_stacked_{'layer_' if layer else ''}{_DTYPE_SUFFIX[src.dtype]}")
+    epilogue = (None if bias is None else bias.data_ptr(),) if layer else ()
+    pitch = (n_cols, out.stride(0)) if layer else ()
+    with _OnDevice(src.device):
+        rc = fn(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), *epilogue, J, S, stride,
+                d.bit_length() - 1, *pitch, flags, _stream(src))
+    _check(rc, "whvi_" + name)
+    return out
+
+
 def fused_shs_stacked_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
     """Shapes the one-launch rectangular fastfood layer covers (``whvi_fused_shs_stacked_supported``, restated: no library
     needed): float32, 64 <= D <= 2048 and ``n_blocks >= 1`` triples of ``D`` floats within 64 KiB of LDS."""
-    if dtype != torch.float32 or d < 1 or (d & (d - 1)) != 0:
-        return False
-    return 64 <= d <= 2048 and n_blocks >= 1 and 12 * d * n_blocks <= 65536
+    return _stacked_fwd_rule(dtype, _F32_DTYPES, d, n_blocks, False)
 
 
 def fused_shs_stacked(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int, sample_stride: int,
@@ -521,42 +593,14 @@ def fused_shs_stacked(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: to
     (sample, row) order -- or ``(sample_stride, D)`` with ``shared``, read by every sample -- ``a, c`` ``(J, D)`` and ``b``
     ``(J, n_samples, D)``.  Block ``j`` of the result has the bits of ``fused_shs(src, a[j], b[j], c[j])``.  ``out``: a
     contiguous, 16-byte aligned ``(n_samples * sample_stride, J * D)`` float32 tensor to write instead of a new one."""
-    S, stride = int(n_samples), int(sample_stride)
-    if src.device.type != "cuda" or src.dim() != 2:
-        raise RuntimeError("fused_shs_stacked: src must be a 2-D CUDA tensor")
-    _require_f32_on_one_device("fused_shs_stacked", src.device, (src, a, b, c))
-    d = src.size(1)
-    if a.dim() != 2 or a.size(1) != d:
-        raise RuntimeError("fused_shs_stacked: a must be (n_blocks, D)")
-    J = a.size(0)
-    if not fused_shs_stacked_supported(torch.float32, d, J):
-        raise RuntimeError(f"fused_shs_stacked: {J} blocks of {d} elements are outside the supported range "
-                           "(64 <= D <= 2048, 12 * D * n_blocks <= 65536)")
-    rows = S * stride
-    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d):
-        raise RuntimeError("fused_shs_stacked: operand shapes do not match (src rows must be n_samples * sample_stride, or "
-                           "sample_stride when shared; a, c (J, D); b (J, S, D))")
-    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
-    if out is None:
-        out = torch.empty((rows, J * d), dtype=torch.float32, device=src.device)
-    elif not out.is_contiguous() or tuple(out.shape) != (rows, J * d) or out.dtype != torch.float32 or out.device != src.device:
-        raise RuntimeError("fused_shs_stacked: bad out tensor")
-    if rows == 0:
-        return out
-    with _OnDevice(src.device):
-        rc = lib().whvi_fused_shs_stacked_f32(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride,
-                                              d.bit_length() - 1, FUSED_SRC_SHARED if shared else 0, _stream(src))
-    _check(rc, "whvi_fused_shs_stacked")
-    return out
+    return _fused_shs_stacked_fwd("fused_shs_stacked", _F32_DTYPES, False, src, a, b, c, n_samples, sample_stride, shared, out)
 
 
 def fused_shs_stacked16_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:
     """Shapes the one-launch rectangular fastfood layer covers on 16-bit activations (``whvi_fused_shs_stacked16_supported``,
     restated: no library needed): float16 / bfloat16, and ``fused_shs_stacked_supported``'s rule for the float32 vectors --
     64 <= D <= 2048 and ``n_blocks >= 1`` triples of ``D`` floats within 64 KiB of LDS."""
-    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
-        return False
-    return 64 <= d <= 2048 and n_blocks >= 1 and 12 * d * n_blocks <= 65536
+    return _stacked_fwd_rule(dtype, _HALF_DTYPES, d, n_blocks, False)
 
 
 def fused_shs_stacked16(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int, sample_stride: int,
@@ -566,43 +610,14 @@ def fused_shs_stacked16(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: 
     rounded ONCE when it is stored.  Block ``j`` has the bits of ``fused_shs(src, a[j], b[j], c[j])`` -- with ``shared``
     (``src`` ``(sample_stride, D)``, read by every sample) of that launch on ``src.repeat(n_samples, 1)``.  ``out``: a
     contiguous, 16-byte aligned ``(n_samples * sample_stride, J * D)`` tensor of ``src``'s dtype to write instead of a new one."""
-    S, stride = int(n_samples), int(sample_stride)
-    if src.device.type != "cuda" or src.dim() != 2 or src.dtype not in _HALF_DTYPES:
-        raise RuntimeError("fused_shs_stacked16: src must be a 2-D float16 / bfloat16 CUDA tensor")
-    _require_f32_on_one_device("fused_shs_stacked16 (16-bit activations: a, b, c)", src.device, (a, b, c))
-    d = src.size(1)
-    if a.dim() != 2 or a.size(1) != d:
-        raise RuntimeError("fused_shs_stacked16: a must be (n_blocks, D)")
-    J = a.size(0)
-    if not fused_shs_stacked16_supported(src.dtype, d, J):
-        raise RuntimeError(f"fused_shs_stacked16: {J} blocks of {d} elements are outside the supported range "
-                           "(64 <= D <= 2048, 12 * D * n_blocks <= 65536)")
-    rows = S * stride
-    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d):
-        raise RuntimeError("fused_shs_stacked16: operand shapes do not match (src rows must be n_samples * sample_stride, or "
-                           "sample_stride when shared; a, c (J, D); b (J, S, D))")
-    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
-    if out is None:
-        out = torch.empty((rows, J * d), dtype=src.dtype, device=src.device)
-    elif not out.is_contiguous() or tuple(out.shape) != (rows, J * d) or out.dtype != src.dtype or out.device != src.device:
-        raise RuntimeError("fused_shs_stacked16: bad out tensor")
-    if rows == 0:
-        return out
-    fn = getattr(lib(), "whvi_fused_shs_stacked_" + _DTYPE_SUFFIX[src.dtype])
-    with _OnDevice(src.device):
-        rc = fn(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(), J, S, stride, d.bit_length() - 1,
-                FUSED_SRC_SHARED if shared else 0, _stream(src))
-    _check(rc, "whvi_fused_shs_stacked16")
-    return out
+    return _fused_shs_stacked_fwd("fused_shs_stacked16", _HALF_DTYPES, False, src, a, b, c, n_samples, sample_stride, shared, out)
 
 
 def fused_shs_stacked_layer_supported(dtype: torch.dtype, d: int, n_blocks: int, has_bias: bool) -> bool:
     """Shapes the one-launch rectangular fastfood layer with its epilogue covers (``whvi_fused_shs_stacked_layer_supported``,
     restated: no library needed): float32, 64 <= D <= 2048 and ``n_blocks >= 1`` triples of ``D`` floats -- quadruples with a
     bias, which is staged with them -- within 64 KiB of LDS."""
-    if dtype != torch.float32 or d < 1 or (d & (d - 1)) != 0:
-        return False
-    return 64 <= d <= 2048 and n_blocks >= 1 and (16 if has_bias else 12) * d * n_blocks <= 65536
+    return _stacked_fwd_rule(dtype, _F32_DTYPES, d, n_blocks, has_bias)
 
 
 def fused_shs_stacked_layer(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int,
@@ -614,42 +629,8 @@ def fused_shs_stacked_layer(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor,
     None (no add at all); ``relu_in`` / ``relu_out``: ``torch.relu`` in front of / behind the layer.  Returns ``(rows, n_cols)``:
     a new contiguous tensor, or ``out`` -- a 2-D float32 tensor with ``stride(1) == 1``, ``stride(0) % 4 == 0``, ``stride(0) >=
     n_cols`` and a 16-byte aligned base, whose row stride is the launch's pitch; its columns past ``n_cols`` are not written."""
-    S, stride = int(n_samples), int(sample_stride)
-    if src.device.type != "cuda" or src.dim() != 2:
-        raise RuntimeError("fused_shs_stacked_layer: src must be a 2-D CUDA tensor")
-    _require_f32_on_one_device("fused_shs_stacked_layer", src.device, (src, a, b, c) + (() if bias is None else (bias,)))
-    d = src.size(1)
-    if a.dim() != 2 or a.size(1) != d:
-        raise RuntimeError("fused_shs_stacked_layer: a must be (n_blocks, D)")
-    J = a.size(0)
-    if not fused_shs_stacked_layer_supported(torch.float32, d, J, bias is not None):
-        raise RuntimeError(f"fused_shs_stacked_layer: {J} blocks of {d} elements {'with' if bias is not None else 'without'} a bias "
-                           "are outside the supported range (64 <= D <= 2048, (12 + 4 * bias) * D * n_blocks <= 65536)")
-    rows = S * stride
-    n_cols = J * d if n_cols is None else int(n_cols)
-    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d) or \
-            (bias is not None and bias.numel() != J * d):
-        raise RuntimeError("fused_shs_stacked_layer: operand shapes do not match (src rows must be n_samples * sample_stride, or "
-                           "sample_stride when shared; a, c (J, D); b (J, S, D); bias J * D elements)")
-    if n_cols % 4 != 0 or not (J - 1) * d < n_cols <= J * d:
-        raise RuntimeError(f"fused_shs_stacked_layer: n_cols = {n_cols} must be a multiple of 4 in ({(J - 1) * d}, {J * d}]")
-    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
-    if bias is not None:
-        bias = _aligned(bias)
-    if out is None:
-        out = torch.empty((rows, n_cols), dtype=torch.float32, device=src.device)
-    elif (out.dim() != 2 or tuple(out.shape) != (rows, n_cols) or out.dtype != torch.float32 or out.device != src.device
-          or (rows > 0 and (out.stride(1) != 1 or out.stride(0) % 4 != 0 or out.stride(0) < n_cols)) or out.data_ptr() % 16 != 0):
-        raise RuntimeError("fused_shs_stacked_layer: bad out tensor")
-    if rows == 0:
-        return out
-    flags = (FUSED_SRC_SHARED if shared else 0) | (FUSED_RELU_IN if relu_in else 0) | (FUSED_RELU_OUT if relu_out else 0)
-    with _OnDevice(src.device):
-        rc = lib().whvi_fused_shs_stacked_layer_f32(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-                                                    None if bias is None else bias.data_ptr(), J, S, stride, d.bit_length() - 1,
-                                                    n_cols, out.stride(0), flags, _stream(src))
-    _check(rc, "whvi_fused_shs_stacked_layer")
-    return out
+    return _fused_shs_stacked_fwd("fused_shs_stacked_layer", _F32_DTYPES, True, src, a, b, c, n_samples, sample_stride, shared, out,
+                                  bias, n_cols, relu_in, relu_out)
 
 
 def fused_shs_stacked_layer16_supported(dtype: torch.dtype, d: int, n_blocks: int, has_bias: bool) -> bool:
@@ -657,9 +638,7 @@ def fused_shs_stacked_layer16_supported(dtype: torch.dtype, d: int, n_blocks: in
     (``whvi_fused_shs_stacked_layer16_supported``, restated: no library needed): float16 / bfloat16, and
     ``fused_shs_stacked_layer_supported``'s rule for the float32 vectors and bias -- 64 <= D <= 2048 and ``n_blocks >= 1`` triples
     of ``D`` floats, quadruples with a bias, within 64 KiB of LDS."""
-    if dtype not in _HALF_DTYPES or d < 1 or (d & (d - 1)) != 0:
-        return False
-    return 64 <= d <= 2048 and n_blocks >= 1 and (16 if has_bias else 12) * d * n_blocks <= 65536
+    return _stacked_fwd_rule(dtype, _HALF_DTYPES, d, n_blocks, has_bias)
 
 
 def fused_shs_stacked_layer16(src: torch.Tensor, a: torch.Tensor, b: torch.Tensor, c: torch.Tensor, n_samples: int,
@@ -673,44 +652,8 @@ def fused_shs_stacked_layer16(src: torch.Tensor, a: torch.Tensor, b: torch.Tenso
     a new contiguous tensor, or ``out`` -- a 2-D tensor of ``src``'s dtype with ``stride(1) == 1``, ``stride(0) % 8 == 0``,
     ``stride(0) >= n_cols`` and a 16-byte aligned base, whose row stride is the launch's pitch; its columns past ``n_cols`` are
     not written."""
-    S, stride = int(n_samples), int(sample_stride)
-    if src.device.type != "cuda" or src.dim() != 2 or src.dtype not in _HALF_DTYPES:
-        raise RuntimeError("fused_shs_stacked_layer16: src must be a 2-D float16 / bfloat16 CUDA tensor")
-    _require_f32_on_one_device("fused_shs_stacked_layer16 (16-bit activations: a, b, c, bias)", src.device,
-                               (a, b, c) + (() if bias is None else (bias,)))
-    d = src.size(1)
-    if a.dim() != 2 or a.size(1) != d:
-        raise RuntimeError("fused_shs_stacked_layer16: a must be (n_blocks, D)")
-    J = a.size(0)
-    if not fused_shs_stacked_layer16_supported(src.dtype, d, J, bias is not None):
-        raise RuntimeError(f"fused_shs_stacked_layer16: {J} blocks of {d} elements {'with' if bias is not None else 'without'} a "
-                           "bias are outside the supported range (64 <= D <= 2048, (12 + 4 * bias) * D * n_blocks <= 65536)")
-    rows = S * stride
-    n_cols = J * d if n_cols is None else int(n_cols)
-    if src.size(0) != (stride if shared else rows) or tuple(c.shape) != (J, d) or tuple(b.shape) != (J, S, d) or \
-            (bias is not None and bias.numel() != J * d):
-        raise RuntimeError("fused_shs_stacked_layer16: operand shapes do not match (src rows must be n_samples * sample_stride, or "
-                           "sample_stride when shared; a, c (J, D); b (J, S, D); bias J * D elements)")
-    if n_cols % 8 != 0 or not (J - 1) * d < n_cols <= J * d:
-        raise RuntimeError(f"fused_shs_stacked_layer16: n_cols = {n_cols} must be a multiple of 8 in ({(J - 1) * d}, {J * d}]")
-    src, a, b, c = (_aligned(t) for t in (src, a, b, c))
-    if bias is not None:
-        bias = _aligned(bias)
-    if out is None:
-        out = torch.empty((rows, n_cols), dtype=src.dtype, device=src.device)
-    elif (out.dim() != 2 or tuple(out.shape) != (rows, n_cols) or out.dtype != src.dtype or out.device != src.device
-          or (rows > 0 and (out.stride(1) != 1 or out.stride(0) % 8 != 0 or out.stride(0) < n_cols)) or out.data_ptr() % 16 != 0):
-        raise RuntimeError("fused_shs_stacked_layer16: bad out tensor")
-    if rows == 0:
-        return out
-    flags = (FUSED_SRC_SHARED if shared else 0) | (FUSED_RELU_IN if relu_in else 0) | (FUSED_RELU_OUT if relu_out else 0)
-    fn = getattr(lib(), "whvi_fused_shs_stacked_layer_" + _DTYPE_SUFFIX[src.dtype])
-    with _OnDevice(src.device):
-        rc = fn(out.data_ptr(), src.data_ptr(), a.data_ptr(), b.data_ptr(), c.data_ptr(),
-                None if bias is None else bias.data_ptr(), J, S, stride, d.bit_length() - 1, n_cols, out.stride(0), flags,
-                _stream(src))
-    _check(rc, "whvi_fused_shs_stacked_layer16")
-    return out
+    return _fused_shs_stacked_fwd("fused_shs_stacked_layer16", _HALF_DTYPES, True, src, a, b, c, n_samples, sample_stride, shared, out,
+                                  bias, n_cols, relu_in, relu_out)
 
 
 def fused_shs_stacked_bwd_supported(dtype: torch.dtype, d: int, n_blocks: int) -> bool:

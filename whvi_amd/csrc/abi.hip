@@ -1,7 +1,6 @@
 // whvi_amd/csrc/abi.hip -- dtype-independent part of the C ABI (include/whvi_hip.h).
 #include "dispatch.hpp"
-#include "fused_stacked16.hpp"
-#include "fused_stacked16_layer.hpp"
+#include "fused_stacked_fwd.hpp"
 
 namespace whvi {
 
@@ -70,101 +69,58 @@ extern "C" __attribute__((visibility("default"))) int whvi_max_log2d(int32_t dty
     }
 }
 
-// ---- the rectangular fastfood layer on 16-bit activations (fused_stacked16.hpp): the support rule and the argument checks,
-// shared by fused_stacked_f16.hip and fused_stacked_bf16.hip
+// ---- the rectangular fastfood layer's forward (fused_stacked_fwd.hpp): the argument checks of all six entries, shared by
+// fused_stacked{,_layer}_{f32,f16,bf16}.hip, and the support rules of the 16-bit entries
 namespace whvi {
 
-// whvi_fused_shs_stacked_f32's checks in its order, with byte extents of 2-byte activations and 4-byte vectors
-int fused_stacked16_check(FusedStackedArgs &r, bool &launch, void *dst, const void *src, const void *a, const void *b,
-                          const void *c, int64_t J, int64_t S, int64_t stride, int32_t log2d, int32_t flags)
+int fused_stacked_fwd_check(const char *what, int esize, bool layer, FusedStackedLayerArgs &r, bool &launch, void *dst,
+                            const void *src, const void *a, const void *b, const void *c, const void *bias, int64_t J, int64_t S,
+                            int64_t stride, int32_t log2d, int64_t n_cols, int64_t ld_dst, int32_t flags)
 {
     g_err[0] = 0;
     launch = false;
-    if (flags & ~WHVI_FUSED_SRC_SHARED)
-        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: unknown fused flags%s 0x%llx (0 or the shared-source flag)", "", flags);
-    if (J < 0 || S < 0 || stride < 0) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: negative size%s", "");
+    if (!layer) bias = nullptr, n_cols = ld_dst = 0;        // (set to J D below, once log2d is known to be in range)
+    if (flags & ~(layer ? WHVI_FUSED_SRC_SHARED | WHVI_FUSED_RELU_IN | WHVI_FUSED_RELU_OUT : WHVI_FUSED_SRC_SHARED))
+        return fail(WHVI_ERR_ARG, layer ? "%s: unknown fused flags 0x%llx (shared source, ReLU in, ReLU out)"
+                                        : "%s: unknown fused flags 0x%llx (0 or the shared-source flag)", what, flags);
+    if (J < 0 || S < 0 || stride < 0 || n_cols < 0 || ld_dst < 0) return fail(WHVI_ERR_ARG, "%s: negative size", what);
     if (log2d < FUSED_STACKED_MIN_LOG2D || log2d > FUSED_STACKED_MAX_LOG2D)
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: log2(D)%s = %lld is outside the supported range [6, %lld]", "", log2d,
-                    FUSED_STACKED_MAX_LOG2D);
-    if (!fused_stacked16_supported(log2d, J))
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: %s%lld blocks need 12 D bytes of LDS each, at most %lld fit 64 KiB", "",
-                    J, FUSED_STACKED_LDS_BYTES / ((int64_t)12 << log2d));
-    if (S == 0 || stride == 0) return WHVI_OK;
-    if (!dst || !src || !a || !b || !c) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked16: null pointer%s", "");
-    if (S >= ((int64_t)1 << 32) / stride)
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: rows are indexed with 32 bits%s", "");
-    if (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15)
-        return fail(WHVI_ERR_ALIGN, "whvi_fused_shs_stacked16: a pointer%s is not 16-byte aligned", "");
-    const FusedBwdGeom geom = fused_bwd_geom(S, stride, log2d);
-    if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked16: too many blocks%s", "");
-    const int64_t row_bytes = (int64_t)2 << log2d, vec_bytes = (int64_t)4 << log2d, rows = S * stride;
-    const bool shared = (flags & WHVI_FUSED_SRC_SHARED) != 0;
-    const struct { const void *p; int64_t bytes; } ins[] = {
-        {src, (shared ? stride : rows) * row_bytes}, {a, J * vec_bytes}, {b, J * S * vec_bytes}, {c, J * vec_bytes}};
-    for (const auto &t : ins)
-        if (ranges_overlap(dst, rows * J * row_bytes, t.p, t.bytes))
-            return fail(WHVI_ERR_OVERLAP, "whvi_fused_shs_stacked16: dst overlaps an input%s", "");
-    r.dst = dst, r.src = src, r.a = a, r.b = b, r.c = c;
-    r.n_blocks = J, r.n_samples = S, r.sample_stride = stride, r.log2d = log2d, r.src_shared = shared, r.geom = geom;
-    // the streamed bytes: the J output segments, and the source unless it is shared
-    r.nt = rows * row_bytes * (J + (shared ? 0 : 1)) > NT_MIN_BYTES;
-    launch = true;
-    return WHVI_OK;
-}
-
-// ---- the same layer with its epilogue folded in (fused_stacked16_layer.hpp), shared by fused_stacked_layer_f16.hip and
-// fused_stacked_layer_bf16.hip: whvi_fused_shs_stacked_layer_f32's checks in its order, with byte extents of 2-byte activations
-// and 4-byte vectors, and n_cols / ld_dst in whole 8-column chunks
-int fused_stacked16_layer_check(FusedStackedLayerArgs &r, bool &launch, void *dst, const void *src, const void *a, const void *b,
-                                const void *c, const void *bias, int64_t J, int64_t S, int64_t stride, int32_t log2d,
-                                int64_t n_cols, int64_t ld_dst, int32_t flags)
-{
-    g_err[0] = 0;
-    launch = false;
-    if (flags & ~(WHVI_FUSED_SRC_SHARED | WHVI_FUSED_RELU_IN | WHVI_FUSED_RELU_OUT))
-        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: unknown fused flags%s 0x%llx (shared source, ReLU in, ReLU out)", "",
-                    flags);
-    if (J < 0 || S < 0 || stride < 0 || n_cols < 0 || ld_dst < 0)
-        return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: negative size%s", "");
-    if (log2d < FUSED_STACKED_MIN_LOG2D || log2d > FUSED_STACKED_MAX_LOG2D)
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: log2(D)%s = %lld is outside the supported range [6, %lld]", "",
-                    log2d, FUSED_STACKED_MAX_LOG2D);
-    const int64_t per_block = (int64_t)(bias ? 16 : 12) << log2d;
-    if (!fused_stacked16_layer_supported(log2d, J, bias != nullptr))
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: %s%lld blocks do not fit 64 KiB of LDS (at most %lld with these operands)",
-                    "", J, FUSED_STACKED_LDS_BYTES / per_block);
-    if ((n_cols | ld_dst) & 7)
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: n_cols%s = %lld and ld_dst = %lld must be multiples of 8", "", n_cols,
-                    ld_dst);
+        return fail(WHVI_ERR_SIZE, "%s: log2(D) = %lld is outside the supported range [6, %lld]", what, log2d, FUSED_STACKED_MAX_LOG2D);
+    if (!fused_stacked_layer_supported(log2d, J, bias != nullptr))
+        return fail(WHVI_ERR_SIZE, layer ? "%s: %lld blocks do not fit 64 KiB of LDS (at most %lld with these operands)"
+                                         : "%s: %lld blocks need 12 D bytes of LDS each, at most %lld fit 64 KiB", what, J,
+                    FUSED_STACKED_LDS_BYTES / ((int64_t)(bias ? 16 : 12) << log2d));
+    if (!layer) n_cols = ld_dst = J << log2d;
+    if ((n_cols | ld_dst) & (16 / esize - 1))               // whole 16-byte chunks: no chunk straddles the edge
+        return fail(WHVI_ERR_SIZE, esize == 4 ? "%s: n_cols = %lld and ld_dst = %lld must be multiples of 4"
+                                              : "%s: n_cols = %lld and ld_dst = %lld must be multiples of 8", what, n_cols, ld_dst);
     if (n_cols <= ((J - 1) << log2d) || n_cols > (J << log2d))
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: n_cols%s = %lld must end in the last of the %lld blocks", "", n_cols,
-                    J);
+        return fail(WHVI_ERR_SIZE, "%s: n_cols = %lld must end in the last of the %lld blocks", what, n_cols, J);
     if (ld_dst < n_cols || ld_dst >= ((int64_t)1 << 32))
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: ld_dst%s = %lld is below n_cols = %lld (or beyond 32 bits)", "", ld_dst,
-                    n_cols);
+        return fail(WHVI_ERR_SIZE, "%s: ld_dst = %lld is below n_cols = %lld (or beyond 32 bits)", what, ld_dst, n_cols);
     if (S == 0 || stride == 0) return WHVI_OK;
-    if (!dst || !src || !a || !b || !c) return fail(WHVI_ERR_ARG, "whvi_fused_shs_stacked_layer16: null pointer%s", "");
-    if (S >= ((int64_t)1 << 32) / stride)
-        return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: rows are indexed with 32 bits%s", "");
+    if (!dst || !src || !a || !b || !c) return fail(WHVI_ERR_ARG, "%s: null pointer", what);
+    if (S >= ((int64_t)1 << 32) / stride) return fail(WHVI_ERR_SIZE, "%s: rows are indexed with 32 bits", what);
     if (((uintptr_t)dst | (uintptr_t)src | (uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)bias) & 15)
-        return fail(WHVI_ERR_ALIGN, "whvi_fused_shs_stacked_layer16: a pointer%s is not 16-byte aligned", "");
+        return fail(WHVI_ERR_ALIGN, "%s: a pointer is not 16-byte aligned", what);
     const FusedBwdGeom geom = fused_bwd_geom(S, stride, log2d);
-    if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "whvi_fused_shs_stacked_layer16: too many blocks%s", "");
-    const int64_t row_bytes = (int64_t)2 << log2d, vec_bytes = (int64_t)4 << log2d, rows = S * stride;
+    if (S * geom.n_slabs >= ((int64_t)1 << 31)) return fail(WHVI_ERR_SIZE, "%s: too many blocks", what);
+    // byte extents: activations of esize bytes, float32 vectors and bias
+    const int64_t row_bytes = (int64_t)esize << log2d, vec_bytes = (int64_t)4 << log2d, rows = S * stride;
     const bool shared = (flags & WHVI_FUSED_SRC_SHARED) != 0;
     const struct { const void *p; int64_t bytes; } ins[] = {
         {src, (shared ? stride : rows) * row_bytes}, {a, J * vec_bytes}, {b, J * S * vec_bytes}, {c, J * vec_bytes},
         {bias, bias ? J * vec_bytes : 0}};
     for (const auto &t : ins)
-        if (t.bytes && ranges_overlap(dst, rows * ld_dst * 2, t.p, t.bytes))
-            return fail(WHVI_ERR_OVERLAP, "whvi_fused_shs_stacked_layer16: dst overlaps an input%s", "");
+        if (t.bytes && ranges_overlap(dst, rows * ld_dst * esize, t.p, t.bytes))
+            return fail(WHVI_ERR_OVERLAP, "%s: dst overlaps an input", what);
     r.dst = dst, r.src = src, r.a = a, r.b = b, r.c = c, r.bias = bias;
     r.n_blocks = J, r.n_samples = S, r.sample_stride = stride, r.n_cols = n_cols, r.ld_dst = ld_dst, r.log2d = log2d;
     r.opts = ((flags & WHVI_FUSED_RELU_IN) ? STACKED_OPT_RELU_IN : 0u) | ((flags & WHVI_FUSED_RELU_OUT) ? STACKED_OPT_RELU_OUT : 0u) |
              (bias ? STACKED_OPT_BIAS : 0u);
     r.src_shared = shared, r.geom = geom;
     // the streamed bytes: the n_cols written columns, and the source unless it is shared
-    r.nt = rows * (2 * n_cols + (shared ? 0 : row_bytes)) > NT_MIN_BYTES;
+    r.nt = rows * (esize * n_cols + (shared ? 0 : row_bytes)) > NT_MIN_BYTES;
     launch = true;
     return WHVI_OK;
 }
@@ -173,13 +129,13 @@ int fused_stacked16_layer_check(FusedStackedLayerArgs &r, bool &launch, void *ds
 
 extern "C" __attribute__((visibility("default"))) int whvi_fused_shs_stacked16_supported(int32_t log2d, int64_t n_blocks)
 {
-    return fused_stacked16_supported(log2d, n_blocks) ? 1 : 0;
+    return fused_stacked_supported(log2d, n_blocks) ? 1 : 0;
 }
 
 extern "C" __attribute__((visibility("default")))
 int whvi_fused_shs_stacked_layer16_supported(int32_t log2d, int64_t n_blocks, int32_t has_bias)
 {
-    return fused_stacked16_layer_supported(log2d, n_blocks, has_bias != 0) ? 1 : 0;
+    return fused_stacked_layer_supported(log2d, n_blocks, has_bias != 0) ? 1 : 0;
 }
 
 // The launch form of whvi_fused_shs_ex_<dtype> for these arguments (include/whvi_hip.h): what fused_plan, the function the

@@ -1,5 +1,5 @@
 #pragma once
-// whvi_amd/csrc/fused_stacked_bwd.hpp -- backward of the rectangular fastfood layer (fused_stacked.hpp: J square operators on the
+// whvi_amd/csrc/fused_stacked_bwd.hpp -- backward of the rectangular fastfood layer (fused_stacked_fwd.hpp: J square operators on the
 // same rows, their outputs side by side) in ONE launch plus a tiny finishing launch: grad_x and the 3 J parameter gradients for
 // all Monte-Carlo samples from grad_y (rows of J D) and x (rows of D), without a copy of a segment of grad_y, a per-block grad_x
 // or a running sum in memory.  ABI: include/whvi_hip.h (whvi_fused_shs_stacked_bwd_f32).

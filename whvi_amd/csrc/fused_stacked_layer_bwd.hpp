@@ -1,6 +1,6 @@
 #pragma once
 // whvi_amd/csrc/fused_stacked_layer_bwd.hpp -- backward of the rectangular fastfood layer WITH its epilogue
-// (fused_stacked_layer.hpp: bias, the neighbouring ReLUs, the narrowing to n_cols) in ONE launch plus a tiny finishing launch:
+// (fused_stacked_fwd.hpp: bias, the neighbouring ReLUs, the narrowing to n_cols) in ONE launch plus a tiny finishing launch:
 // fused_stacked_bwd.hpp's launch with the two masks, the zero padding and the bias sum folded in, so that no masked or padded
 // copy of grad_y, no relu(x) and no unmasked grad_x exists in memory.  ABI: include/whvi_hip.h
 // (whvi_fused_shs_stacked_layer_bwd_f32).
