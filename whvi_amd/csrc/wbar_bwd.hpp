@@ -110,7 +110,7 @@ wbar_bwd_kernel(T *grad_u, T *part_s1, T *part_s2, const u32x4 *gw, const T *__r
     struct Rows {
         uint32_t ri[NACC];           // row index i inside its matrix
         size_t ro[NACC];             // offset of the row's three outputs (laid out like u)
-        A uv[NACC], uv0[NACC], s2v[NACC], gii[NACC];
+        A uv[NACC], s2v[NACC], gii[NACC];   // uv: u_k, under MEAN u_k + u_mean
     };
     // rows past the end read row 0's operands (valid memory, results discarded)
     auto row_index = [&](int64_t tile, int n, uint32_t &rr, uint32_t &i, uint32_t &j, uint32_t &ur) {
@@ -151,8 +151,10 @@ wbar_bwd_kernel(T *grad_u, T *part_s1, T *part_s2, const u32x4 *gw, const T *__r
             rw.ro[n] = (size_t)ur * D + i;
             rw.s2v[n] = (A)s2[(size_t)j * D + i];
             rw.uv[n] = (A)u[(size_t)ur * D + i];
-            if constexpr (MEAN) rw.uv0[n] = (A)u[(size_t)(j * by_s.d + j) * D + i];
-            else rw.uv0[n] = (A)0;
+            // MEAN: W[j,k] is linear in u, so its s1 / s2 gradients see u_k + u_mean: ONE rounded sum, then the products of the
+            // plain form.  (The two products formed separately and added lose every digit the sum cancels: per element the
+            // error was e (|u_k| + |u_mean|) ... against a result of size |u_k + u_mean| -- tests/test_wbar_table_gpu.py (c).)
+            if constexpr (MEAN) rw.uv[n] += (A)u[(size_t)(j * by_s.d + j) * D + i];
             rw.gii[n] = (A)reinterpret_cast<const T *>(gw)[(size_t)rr * D + i];   // dL/dW[row, i]: a line this tile loads anyway
         }
     };
@@ -176,7 +178,7 @@ wbar_bwd_kernel(T *grad_u, T *part_s1, T *part_s2, const u32x4 *gw, const T *__r
         }
     };
     // c = (H g1)[i] by a pruned butterfly over the row's elements d = (kk * 64 + lane_col) * VEC + e, then
-    // dL/du = s2_i c, dL/ds2 = u_i c (+ u0_i c); one lane per row writes the three results
+    // dL/du = s2_i c, dL/ds2 = (u_i [+ u0_i]) c; one lane per row writes the three results
     auto sums_out = [&](int64_t tile, const Rows &rw, A (&r)[K][VEC]) {
 #pragma unroll
         for (int n = 0; n < NACC; ++n) {
@@ -213,15 +215,9 @@ wbar_bwd_kernel(T *grad_u, T *part_s1, T *part_s2, const u32x4 *gw, const T *__r
             const uint32_t row = first_row(tile, n * KPR);
             const bool writer = (SH >= 6) ? (lane == 0) : (lane_col == 0);
             if (writer && row < n_rows) {
-                A p1 = rw.gii[n] * ((A)D * (rw.uv[n] * rw.s2v[n]));
-                A p2 = rw.uv[n] * c;
-                if constexpr (MEAN) {
-                    p1 += rw.gii[n] * ((A)D * (rw.uv0[n] * rw.s2v[n]));
-                    p2 += rw.uv0[n] * c;
-                }
                 grad_u[rw.ro[n]] = (T)(c * rw.s2v[n]);
-                part_s2[rw.ro[n]] = (T)p2;
-                part_s1[rw.ro[n]] = (T)p1;
+                part_s2[rw.ro[n]] = (T)(rw.uv[n] * c);
+                part_s1[rw.ro[n]] = (T)(rw.gii[n] * ((A)D * (rw.uv[n] * rw.s2v[n])));
             }
         }
     };
